@@ -12,6 +12,14 @@ content is synthetic (random targets): the lego dataset is not available here.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp16|fp32]
                     [--num-samples 64 --num-samples-fine 128] [--global-batch G] [--pose-opt]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric,
+value, unit, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step
+returned (and the parameters it left) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.  --full adds everything else the benchmark
+measures: the per-kernel timings and rooflines, the recorded PSNR comparison, the batch
+assembly cost, the trained-state leg and the CPU baseline.
 
 (BASELINE cfg #5 is --precision fp16 --num-samples 128 --num-samples-fine 256; cfg #3 is
 --pose-opt; cfg #4's strong-scaling leg is --global-batch 4096 under torchrun, where every
@@ -591,6 +599,8 @@ def eval_bench(args, dev, world: int, rank: int, pg):
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt)
     assert torch.isfinite(out["rgb"]).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)  # the last rendered view
     rays = H * W
     value = world * rays * args.steps / dt
     evals = rcfg.num_samples + (rcfg.num_samples + rcfg.num_samples_fine)
@@ -626,6 +636,25 @@ def eval_bench(args, dev, world: int, rank: int, pg):
     }
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname: str, arrays) -> None:
+    """Write {name: tensor} as <dirname>/<name>.npy (float32; float64 stays float64).
+    Every array gets an equal share of DUMP_BYTES; a larger one is cut to a fixed, seeded
+    sample of its flattened elements (ascending indices)."""
+    arrays = {k: v for k, v in arrays.items() if isinstance(v, torch.Tensor)}
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    cap = DUMP_BYTES // 8 // max(1, len(arrays))  # elements per array
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(d / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -656,6 +685,13 @@ def main():
                          "graph); auto (default): only in a graph replay of <= 1024 rays, where it pays")
     ap.add_argument("--pose-opt", action="store_true",
                     help="BASELINE cfg #3: joint pose optimisation step (train_pose_opt, poses optimising)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (losses, rgb_fine) and the "
+                         "parameters it left as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline: per-kernel timings and "
+                         "rooflines, the recorded PSNR comparison, the batch assembly cost, the trained-state "
+                         "leg (--no-trained skips it) and the CPU baseline (--no-cpu-baseline skips it)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 10 if args.eval else 200
@@ -748,30 +784,32 @@ def main():
         o, d, t = pool[k % len(pool)]
         return trainer.step(o, d, t)
 
-    # every fused-MLP entry point is timed over the last warm-up steps (kernel_ms) to find
-    # the dominant kernel; inside the timed region only that kernel's launches carry HIP
-    # events (each bracketed call costs a few us of queue gap)
+    # --full: every fused-MLP entry point is timed over the last warm-up steps (kernel_ms)
+    # to find the dominant kernel; inside the timed region only that kernel's launches
+    # carry HIP events (each bracketed call costs a few us of queue gap).  A plain run
+    # brackets nothing
     mlp_entries = ["nr_mlp_forward", "nr_mlp_backward_dx", "nr_mlp_backward_dw", "nr_mlp_backward_reduce"]
-    wtimer = _hip.CallTimer(mlp_entries)
+    wtimer = _hip.CallTimer(mlp_entries) if args.full else None
     # the data-parallel all-reduce is timed over the same warm-up steps (HIP events around
     # GradAllReducer's launch and wait), not inside the timed region: at small host-bound
     # batches the extra event records would lengthen the measured steps
     reducer = getattr(trainer, "reducer", None)
     for k in range(args.warmup):
         if k == args.warmup // 2:
-            _hip.set_timer(wtimer)
             if reducer is not None:
                 reducer.timing = []
-            for net in (mc, mf):  # the backward's active-tile counts (work it executed)
-                net._tile_counts = []
+            if args.full:
+                _hip.set_timer(wtimer)
+                for net in (mc, mf):  # the backward's active-tile counts (work it executed)
+                    net._tile_counts = []
         step(k)
     _hip.set_timer(None)
     torch.cuda.synchronize()
-    active = active_tile_fracs(mc, mf)
+    active = active_tile_fracs(mc, mf) if args.full else {}
     ar_timing = reducer.timing_summary() if reducer is not None else None
     if reducer is not None:
         reducer.timing = None
-    wcalls = wtimer.summary()
+    wcalls = wtimer.summary() if args.full else {}
     # dominant kernel = largest total time per step (no warm-up: time them all live)
     dom_key = max(wcalls, key=lambda k: wcalls[k][0] * wcalls[k][1]) if wcalls else None
 
@@ -790,7 +828,7 @@ def main():
             return gtr.step(o, d, t)
         for k in range(3):
             step(k)
-    timer = _hip.CallTimer(mlp_entries, keys=[dom_key] if dom_key else None)
+    timer = _hip.CallTimer(mlp_entries, keys=[dom_key] if dom_key else None) if args.full else None
     _hip.set_timer(timer)
     if pg is not None:
         torch.distributed.barrier()
@@ -819,29 +857,37 @@ def main():
     topology = None
     if pg is not None:
         topology = rank_topology(pg, dev, step_pcts[1], ar_timing)
-    calls = timer.summary() if not args.graph else {dom_key: wcalls[dom_key]}
-    if dom_key is None:
-        wcalls = calls
-        dom_key = max(calls, key=lambda k: calls[k][0] * calls[k][1])
-    n_launch, ms = calls[dom_key]  # live, over the timed region
-    entry, M = dom_key.split("[M=")[0], int(dom_key.split("[M=")[1].rstrip("]"))
-    kern = KERNEL_OF.get(entry, (entry,))
-    dom_traffic = traffic_of(kern, M, args.precision)
-    n_params = mf.flat_params().numel()
-    bound, achieved, peak, unit, work = roofline_of(entry, M, ms, args.precision, n_params, dom_traffic)
-    mf_tf, _, mf_work = mfma_roofline(entry, M, ms, args.precision)
-    dom_active = active.get(M, 1.0) if entry != "nr_mlp_forward" else 1.0
-    if not mfma_macs_of(entry):
-        # a dominant launch without MFMA work (e.g. the slab reduction): its byte roofline
-        mf_tf, mf_work = None, work
-    elif dom_active < 1.0:
-        mf_work += f" x active-tile fraction {dom_active:.4f}"
-    # the committed rocprofv3 kernel trace of this tree (same bench command): its average
-    # for the dominant kernel, and the fraction it gives
-    rp_rows, rp_src = rocprof_summary(args.precision)
-    rp = next((rp_rows[(k, M)] for k in kern if (k, M) in rp_rows), None)
-    rp_ms = float(rp.get("timed_avg_ms") or rp["avg_ms"]) if rp else None
-    ktab, step_bytes = kernel_table(wcalls, args.precision, n_params, rp_rows, active)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step holds after the last one: the metrics it returned
+        # and the parameters (and, with --pose-opt, the poses) it left
+        arrays = dict(m, params_coarse=mc.flat_params(), params_fine=mf.flat_params())
+        if args.pose_opt:
+            arrays["poses"] = torch.cat([p.detach().reshape(-1) for p in cam.parameters()])
+        dump_outputs(args.dump_outputs, arrays)
+    if args.full:
+        calls = timer.summary() if not args.graph else {dom_key: wcalls[dom_key]}
+        if dom_key is None:
+            wcalls = calls
+            dom_key = max(calls, key=lambda k: calls[k][0] * calls[k][1])
+        n_launch, ms = calls[dom_key]  # live, over the timed region
+        entry, M = dom_key.split("[M=")[0], int(dom_key.split("[M=")[1].rstrip("]"))
+        kern = KERNEL_OF.get(entry, (entry,))
+        dom_traffic = traffic_of(kern, M, args.precision)
+        n_params = mf.flat_params().numel()
+        bound, achieved, peak, unit, work = roofline_of(entry, M, ms, args.precision, n_params, dom_traffic)
+        mf_tf, _, mf_work = mfma_roofline(entry, M, ms, args.precision)
+        dom_active = active.get(M, 1.0) if entry != "nr_mlp_forward" else 1.0
+        if not mfma_macs_of(entry):
+            # a dominant launch without MFMA work (e.g. the slab reduction): its byte roofline
+            mf_tf, mf_work = None, work
+        elif dom_active < 1.0:
+            mf_work += f" x active-tile fraction {dom_active:.4f}"
+        # the committed rocprofv3 kernel trace of this tree (same bench command): its average
+        # for the dominant kernel, and the fraction it gives
+        rp_rows, rp_src = rocprof_summary(args.precision)
+        rp = next((rp_rows[(k, M)] for k in kern if (k, M) in rp_rows), None)
+        rp_ms = float(rp.get("timed_avg_ms") or rp["avg_ms"]) if rp else None
+        ktab, step_bytes = kernel_table(wcalls, args.precision, n_params, rp_rows, active)
     value = world * B * args.steps / dt
     out = {
         "metric": METRIC,
@@ -871,69 +917,72 @@ def main():
             **({"coarse_stream": "coarse chain on a second stream"}
                if getattr(trainer, "last_step_coarse_stream", False) else {}),
         },
-        # headline: the dominant kernel on SURVEY §8d's MFMA basis (algorithmic FLOPs per
-        # launch over its launch time); the stored-activation HBM view rides beside it
-        "roofline": {
-            # frac: from the committed rocprof kernel-trace average of these sources when
-            # one exists (reproducible from profiles/), else from the live launch time;
-            # MFMA basis, or the byte basis for a launch without MFMA work
-            **(headline_roofline(mf_tf, ms, rp_ms, args.precision, dom_active) if mf_tf is not None else {
-                "bound": bound, "achieved": round(achieved * ms / rp_ms if rp_ms else achieved, 2), "peak": peak,
-                "unit": unit, "frac": round((achieved * ms / rp_ms if rp_ms else achieved) / peak, 4)}),
-            "kernel": f"{kern[0]} via {entry} (M={M} samples, fine net)",
-            "frac_basis": (f"rocprof_ms: timed-region average of {rp_src} (same source_hash)" if rp_ms
-                           else "launch_ms: HIP events on the launching stream over the eager warm-up steps "
-                           "(a graph replay runs no Python)" if args.graph
-                           else "launch_ms: live HIP events on the launching stream over the timed region"),
-            "traffic": dom_traffic,
-            "work_per_launch": mf_work,
-            # the backward's executed share of the 32-sample tiles of this launch (tiles with
-            # a nonzero incoming gradient, counted by the kernels over the warm-up steps)
-            "active_tile_frac": round(dom_active, 4),
-            # HIP events around each launch over the timed region: carries queue gaps, so it
-            # is context only (no fraction is taken from it when a rocprof average exists)
-            "launch_ms_bracketed": round(ms, 4),
-            "launches": n_launch,
-            "rocprof_ms": round(rp_ms, 4) if rp_ms else None,
-            "rocprof_source": rp_src if rp_ms else None,
-            "source_hash": source_hash(),
-            "stored_activation_bytes_design": {
-                "bound": bound, "achieved": round(achieved * ms / rp_ms if rp_ms else achieved, 2), "peak": peak,
-                "unit": unit, "frac": round((achieved * ms / rp_ms if rp_ms else achieved) / peak, 4),
-                "work_per_launch": work,
-                "note": "bytes this decomposition chooses to store and re-read (saved activations, dz), "
-                        "not algorithmic work"},
-        },
-        # per fused-MLP launch: live ms (last warm-up steps), counted PMC bytes and their
-        # rate, MFMA / HBM floors and the bound they give (profiles/traffic.json)
-        "kernels": ktab,
-        # the step's counted MLP bytes over the step time, against 8 TB/s
-        "step_hbm_bytes": step_bytes or None,
-        "step_hbm_frac": round(step_bytes / (dt / args.steps) / (PEAK_HBM_GBS * 1e9), 4) if step_bytes else None,
         # whole-step MFMA fraction: rays/s x training FLOP/ray / (GPUs x peak)
         "step_mfma_frac": round(value * 6 * MACS_PER_EVAL * (2 * rcfg.num_samples + rcfg.num_samples_fine)
                                 / (world * PEAK_TFLOPS[args.precision] * 1e12), 4),
         "step_ms_p10_p50_p90": step_pcts,
-        # per-launch ms of every fused-MLP key: the rocprof timed-region average where the
-        # committed same-source summary has it, else the bracketed warm-up mean (labelled)
-        "kernel_ms": {k: v["ms"] for k, v in ktab.items()},
-        "kernel_ms_source": sorted({v["ms_source"] for v in ktab.values()}),
-        # each key launches once per step: the fused-MLP launches' share of ms_per_step
-        "kernel_ms_sum": round(sum(v["ms"] for v in ktab.values()), 4),
-        "active_tile_frac": {str(k): round(v, 4) for k, v in sorted(active.items())},
         "final_loss": round(loss, 6),
-        # the lego test split is not available offline: the PSNR half of the
-        # metric is the recorded equal-iteration comparison on the analytic scene
-        "psnr": psnr_record(),
     }
+    if args.full:
+        out.update({
+            # headline: the dominant kernel on SURVEY §8d's MFMA basis (algorithmic FLOPs per
+            # launch over its launch time); the stored-activation HBM view rides beside it
+            "roofline": {
+                # frac: from the committed rocprof kernel-trace average of these sources when
+                # one exists (reproducible from profiles/), else from the live launch time;
+                # MFMA basis, or the byte basis for a launch without MFMA work
+                **(headline_roofline(mf_tf, ms, rp_ms, args.precision, dom_active) if mf_tf is not None else {
+                    "bound": bound, "achieved": round(achieved * ms / rp_ms if rp_ms else achieved, 2), "peak": peak,
+                    "unit": unit, "frac": round((achieved * ms / rp_ms if rp_ms else achieved) / peak, 4)}),
+                "kernel": f"{kern[0]} via {entry} (M={M} samples, fine net)",
+                "frac_basis": (f"rocprof_ms: timed-region average of {rp_src} (same source_hash)" if rp_ms
+                               else "launch_ms: HIP events on the launching stream over the eager warm-up steps "
+                               "(a graph replay runs no Python)" if args.graph
+                               else "launch_ms: live HIP events on the launching stream over the timed region"),
+                "traffic": dom_traffic,
+                "work_per_launch": mf_work,
+                # the backward's executed share of the 32-sample tiles of this launch (tiles with
+                # a nonzero incoming gradient, counted by the kernels over the warm-up steps)
+                "active_tile_frac": round(dom_active, 4),
+                # HIP events around each launch over the timed region: carries queue gaps, so it
+                # is context only (no fraction is taken from it when a rocprof average exists)
+                "launch_ms_bracketed": round(ms, 4),
+                "launches": n_launch,
+                "rocprof_ms": round(rp_ms, 4) if rp_ms else None,
+                "rocprof_source": rp_src if rp_ms else None,
+                "source_hash": source_hash(),
+                "stored_activation_bytes_design": {
+                    "bound": bound, "achieved": round(achieved * ms / rp_ms if rp_ms else achieved, 2), "peak": peak,
+                    "unit": unit, "frac": round((achieved * ms / rp_ms if rp_ms else achieved) / peak, 4),
+                    "work_per_launch": work,
+                    "note": "bytes this decomposition chooses to store and re-read (saved activations, dz), "
+                            "not algorithmic work"},
+            },
+            # per fused-MLP launch: live ms (last warm-up steps), counted PMC bytes and their
+            # rate, MFMA / HBM floors and the bound they give (profiles/traffic.json)
+            "kernels": ktab,
+            # the step's counted MLP bytes over the step time, against 8 TB/s
+            "step_hbm_bytes": step_bytes or None,
+            "step_hbm_frac": round(step_bytes / (dt / args.steps) / (PEAK_HBM_GBS * 1e9), 4) if step_bytes else None,
+            # per-launch ms of every fused-MLP key: the rocprof timed-region average where the
+            # committed same-source summary has it, else the bracketed warm-up mean (labelled)
+            "kernel_ms": {k: v["ms"] for k, v in ktab.items()},
+            "kernel_ms_source": sorted({v["ms_source"] for v in ktab.values()}),
+            # each key launches once per step: the fused-MLP launches' share of ms_per_step
+            "kernel_ms_sum": round(sum(v["ms"] for v in ktab.values()), 4),
+            "active_tile_frac": {str(k): round(v, 4) for k, v in sorted(active.items())},
+            # the lego test split is not available offline: the PSNR half of the
+            # metric is the recorded equal-iteration comparison on the analytic scene
+            "psnr": psnr_record(),
+        })
     if topology is not None:
         out["topology"] = topology
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         out["batch_assembly_ms_per_step"] = batch_assembly_ms(dev, B)
-    if (rank == 0 and world == 1 and not args.pose_opt and not args.graph and not strong and not args.no_trained
-            and (rcfg.num_samples, rcfg.num_samples_fine) == (64, 128)):
+    if (args.full and rank == 0 and world == 1 and not args.pose_opt and not args.graph and not strong
+            and not args.no_trained and (rcfg.num_samples, rcfg.num_samples_fine) == (64, 128)):
         out["trained_state"] = trained_state_leg(args.precision, dev, B=B)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.pose_opt:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.pose_opt:
         out["cpu_baseline"] = cpu_baseline(steps=args.cpu_steps)
     if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)

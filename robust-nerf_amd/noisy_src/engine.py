@@ -367,7 +367,12 @@ class GraphedTrainer:
         lr = [g["lr"] for g in opt.param_groups]
         opt.device_sched = self.sched
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        # data parallel: the process group's watchdog thread polls the events of the eager
+        # warm-up's all-reduces until it has seen them complete.  Under the default "global"
+        # capture mode such a query from another thread fails while the capture is open,
+        # and the watchdog then ends the process; "thread_local" checks this thread only
+        mode = "thread_local" if trainer.process_group is not None else "global"
+        with torch.cuda.graph(self.graph, capture_error_mode=mode):
             self.out = trainer.step(*self.static, *self.static_rand)
         for st, v in steps:
             st["step"].copy_(v)

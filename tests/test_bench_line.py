@@ -78,6 +78,28 @@ def test_bracketed_entries_carry_no_fraction():
         assert not any(k.endswith("_frac") or k.endswith("tflops") for k in v), v
 
 
+def test_dump_outputs_float_arrays_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per tensor, float32 (float64 kept), non-tensors left out; an
+    array over its share of the byte budget is cut to the same ascending sample every time."""
+    import numpy as np
+    import torch
+    small = {"rgb": torch.arange(6, dtype=torch.bfloat16).reshape(2, 3), "loss": torch.tensor(0.5, dtype=torch.float64),
+             "steps": 3}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["loss.npy", "rgb.npy"]
+    rgb = np.load(tmp_path / "a" / "rgb.npy")
+    assert rgb.dtype == np.float32 and rgb.tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 2 * 10)  # two arrays: 10 elements each
+    big = {"x": torch.arange(100.0), "y": torch.arange(10.0)}
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    x = np.load(tmp_path / "b" / "x.npy")
+    assert x.shape == (10,) and (np.diff(x) > 0).all() and set(x) <= set(range(100))
+    assert np.array_equal(x, np.load(tmp_path / "c" / "x.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "y.npy"), np.arange(10.0, dtype=np.float32))
+
+
 def test_active_fraction_scales_executed_work():
     """On a skipping backward the dX / dW fractions count the executed tiles only."""
     rows = _summary_rows()
