@@ -145,14 +145,17 @@ int nr_positional_encoding_bwd(const float* x, int64_t M, int C, int num_freqs,
 
 /* ---- A9: sample_pdf  (noisy_src/rays.py:213-279) -------------------------
  * bins (B,Nb), weights (B,Nb-1), u (B,Ns) nullable -> det=True linspace(0,1).
- * samples (B,Ns) in the order of u.                                         */
+ * samples (B,Ns) in the order of u.  Nb <= 4097 (above 513 bins a ray takes a
+ * workgroup of its own); a larger Nb is NR_EARG.                             */
 int nr_sample_pdf(const float* bins, const float* weights, const float* u,
                   int B, int Nb, int Ns, float* samples, nr_stream_t stream);
 
 /* ---- A10: sample_hierarchical  (noisy_src/rays.py:282-333) ---------------
  * z_coarse (B,Nc), w_coarse (B,Nc) -> z_fine (B,Nc+Nf) = sort(cat(z, sample_pdf(
  * mid(z), w[:,1:-1], Nf, det))), pts_fine (B,Nc+Nf,3) nullable.  u nullable=det.
- * viewdirs (B*(Nc+Nf),3) nullable, as in nr_stratified_sample.               */
+ * viewdirs (B*(Nc+Nf),3) nullable, as in nr_stratified_sample.  z_coarse may be
+ * in any order.  Nc + Nf <= 4096 (above 512 a ray takes a workgroup of its own
+ * and is sorted in runs of 512); a larger sum is NR_EARG.                     */
 int nr_sample_hierarchical(const float* rays_o, const float* rays_d,
                            const float* z_coarse, const float* w_coarse,
                            const float* u, int B, int Nc, int Nf,

@@ -8,7 +8,9 @@
 // uniforms; idx = searchsorted(cdf, u, right=True); below/above clamped; the
 // `denom < 1e-5 -> 1` rule; s = b0 + (u-c0)/denom * (b1-b0).  The hierarchical
 // form then sorts cat(z_coarse, s) — here a bitonic sort in the wave's registers, whose
-// output values equal torch.sort's whatever the order of u.
+// output values equal torch.sort's whatever the order of u.  Rays of more than 512
+// values (up to 4096) take one workgroup each and are sorted in runs of 512 (see the
+// long-ray kernels below); the arithmetic per value is the same.
 #include "common.hpp"
 
 namespace nr {
@@ -221,6 +223,197 @@ __global__ void sample_hier_kernel(const float* ro, const float* rd, const float
     }
 }
 
+// ---- Long rays: 512 < Nc + Nf <= 4096 (and 513 < Nb <= 4097 for sample_pdf) ----------
+// One workgroup of four waves per ray, so LDS no longer scales with kRaysPerBlock:
+// bins[nb] | cdf[nb] | wbuf[nb] | sort buffer.  Same arithmetic as above; the kernels
+// above and their dispatch are untouched.
+constexpr int kLongThreads = 256;
+constexpr int kRun = 64 * kMaxPerLane;  // one bitonic_sort<8> run
+constexpr int kLongMaxT = 4096;         // 3 (Nc - 1) + padded T floats stay under 64 KiB
+constexpr int kLongMaxBins = 4097;
+
+// cdf[0..nb-1] from wbuf[0..nb-2] by the whole workgroup (the caller syncs before and
+// after).  The normaliser is a tree reduction; the pdf division runs in place; the
+// cumsum is build_cdf's sequential fp32 recurrence in index order, run by wave 0 on 64
+// values at a time: one coalesced read, 64 dependent adds fed by v_readlane, one
+// coalesced write (instead of a predicated LDS store per element).
+__device__ __forceinline__ void build_cdf_long(float* wbuf, float* cdf, float* red, int nb, int tid) {
+    const int lane = tid & 63, wv = tid >> 6, nw = nb - 1;
+    float part = 0.f;
+    for (int k = tid; k < nw; k += kLongThreads) part += wbuf[k] + 1e-5f;
+#pragma unroll
+    for (int off = 32; off; off >>= 1) part += __shfl_xor(part, off);
+    if (lane == 0) red[wv] = part;
+    __syncthreads();
+    const float sum = (red[0] + red[1]) + (red[2] + red[3]);
+    for (int k = tid; k < nw; k += kLongThreads) wbuf[k] = (wbuf[k] + 1e-5f) / sum;
+    __syncthreads();
+    if (wv != 0) return;
+    float run = 0.f;
+    if (lane == 0) cdf[0] = 0.f;
+    for (int base = 0; base < nw; base += 64) {
+        const int k = base + lane;
+        const float x = k < nw ? wbuf[k] : 0.f;
+        const int cnt = nw - base < 64 ? nw - base : 64;
+        float mine = 0.f;
+        if (cnt == 64) {
+#pragma unroll 1
+            for (int j0 = 0; j0 < 64; j0 += 16) {
+#pragma unroll
+                for (int j = j0; j < j0 + 16; ++j) {
+                    run += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
+                    mine = lane == j ? run : mine;
+                }
+            }
+        } else {
+            for (int j = 0; j < cnt; ++j) {
+                run += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
+                mine = lane == j ? run : mine;
+            }
+        }
+        if (k < nw) cdf[k + 1] = mine;
+    }
+}
+
+__global__ __launch_bounds__(kLongThreads) void sample_pdf_long_kernel(const float* bins_g, const float* w_g,
+                                                                       const float* u_g, int Nb, int Ns, float* out) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float red[kLongThreads / 64];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    float* bins = smem;
+    float* cdf = bins + Nb;
+    float* wbuf = cdf + Nb;
+    for (int i = tid; i < Nb; i += kLongThreads) bins[i] = bins_g[b * Nb + i];
+    for (int i = tid; i < Nb - 1; i += kLongThreads) wbuf[i] = w_g[b * (Nb - 1) + i];
+    __syncthreads();
+    build_cdf_long(wbuf, cdf, red, Nb, tid);
+    __syncthreads();
+    for (int j = tid; j < Ns; j += kLongThreads) {
+        const float u = u_g ? u_g[b * Ns + j] : linspace01(Ns, j);
+        out[b * Ns + j] = invert_cdf(cdf, bins, Nb, u);
+    }
+}
+
+// The T values (coarse z, then the inverse-CDF samples, +inf up to a multiple of kRun)
+// sit in LDS and are sorted in runs of kRun: each run in one wave's registers by
+// bitonic_sort<8>, then every element's place in the output is its index in its own run
+// plus, for each other run, the number of that run's elements before it -- counting
+// `<= x` in runs of lower index and `< x` in runs of higher index, so equal values get
+// distinct places and the places are a permutation of 0..T-1 for any input order.  The
+// padding sorts to the end of the last run, never counts as `< x`, and is never counted
+// with `<=` because no run follows it.
+__global__ __launch_bounds__(kLongThreads) void sample_hier_long_kernel(const float* ro, const float* rd,
+                                                                        const float* zc_g, const float* wc_g,
+                                                                        const float* u_g, int Nc, int Nf,
+                                                                        float* zf_out, float* pts_out,
+                                                                        float* vd_out) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float red[kLongThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t b = blockIdx.x;
+    const int Nb = Nc - 1, T = Nc + Nf;
+    const int NR = ceil_div(T, kRun), P = NR * kRun;
+    float* bins = smem;
+    float* cdf = bins + Nb;
+    float* wbuf = cdf + Nb;
+    float* sbuf = wbuf + Nb;  // P floats
+    const int64_t zb = b * Nc;
+    for (int i = tid; i < Nc; i += kLongThreads) sbuf[i] = zc_g[zb + i];
+    for (int i = tid; i < Nc - 2; i += kLongThreads) wbuf[i] = wc_g[zb + 1 + i];  // weights[..., 1:-1]
+    __syncthreads();
+    for (int i = tid; i < Nb; i += kLongThreads) bins[i] = 0.5f * (sbuf[i + 1] + sbuf[i]);  // z_vals_mid
+    build_cdf_long(wbuf, cdf, red, Nb, tid);  // its first barrier orders bins too
+    __syncthreads();
+    for (int j = tid; j < P - Nc; j += kLongThreads) {
+        float s = __builtin_inff();
+        if (j < Nf) {
+            const float u = u_g ? u_g[b * Nf + j] : linspace01(Nf, j);
+            s = invert_cdf(cdf, bins, Nb, u);
+        }
+        sbuf[Nc + j] = s;
+    }
+    __syncthreads();
+    for (int r = wv; r < NR; r += kLongThreads / 64) {  // a run belongs to one wave
+        float v[kMaxPerLane];
+#pragma unroll
+        for (int i = 0; i < kMaxPerLane; ++i) v[i] = sbuf[r * kRun + i * 64 + lane];
+        bitonic_sort<kMaxPerLane>(v, lane);
+#pragma unroll
+        for (int i = 0; i < kMaxPerLane; ++i) sbuf[r * kRun + i * 64 + lane] = v[i];
+    }
+    __syncthreads();
+    const int64_t ob = b * T;
+    float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
+    if (pts_out || vd_out) {
+        ox = ro ? ro[3 * b] : 0.f, oy = ro ? ro[3 * b + 1] : 0.f, oz = ro ? ro[3 * b + 2] : 0.f;
+        dx = rd[3 * b], dy = rd[3 * b + 1], dz = rd[3 * b + 2];
+    }
+    float vx = 0.f, vy = 0.f, vz = 0.f;
+    if (vd_out) {  // rendering.py:165 (expand_viewdirs_kernel's values)
+        const float dn = norm3(dx, dy, dz);
+        vx = dx / dn, vy = dy / dn, vz = dz / dn;
+    }
+    // Sorted position p = r * kRun + i is a real element exactly when p < T.  Four
+    // elements per thread keep four independent search chains in flight; every search is
+    // the same ten probes of a kRun-long run, so the wave never diverges.
+    constexpr int E = 4;
+    for (int base = 0; base < P; base += E * kLongThreads) {
+        float x[E];
+        int rank[E];
+#pragma unroll
+        for (int k = 0; k < E; ++k) {
+            const int p = base + k * kLongThreads + tid;
+            x[k] = p < T ? sbuf[p] : 0.f;
+            rank[k] = p & (kRun - 1);
+        }
+        for (int qq = 0; qq < NR - 1; ++qq) {  // the other runs
+            int off[E];
+            bool le[E];
+            int pos[E];
+#pragma unroll
+            for (int k = 0; k < E; ++k) {
+                const int r = (base + k * kLongThreads + tid) / kRun;  // may be >= NR past P: q stays < NR
+                const int q = qq + (qq >= r ? 1 : 0);
+                off[k] = q * kRun;
+                le[k] = q < r;
+                pos[k] = 0;
+            }
+#pragma unroll
+            for (int step = kRun / 2; step; step >>= 1) {
+#pragma unroll
+                for (int k = 0; k < E; ++k) {
+                    const float v = sbuf[off[k] + pos[k] + step - 1];
+                    pos[k] += (le[k] ? v <= x[k] : v < x[k]) ? step : 0;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < E; ++k) {  // pos <= kRun - 1 here
+                const float v = sbuf[off[k] + pos[k]];
+                rank[k] += pos[k] + ((le[k] ? v <= x[k] : v < x[k]) ? 1 : 0);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < E; ++k) {
+            const int p = base + k * kLongThreads + tid;
+            if (p < T) {  // rank < T: own index plus at most every real element of the other runs
+                const int64_t o = ob + rank[k];
+                zf_out[o] = x[k];
+                if (pts_out) {
+                    pts_out[3 * o] = ox + dx * x[k];
+                    pts_out[3 * o + 1] = oy + dy * x[k];
+                    pts_out[3 * o + 2] = oz + dz * x[k];
+                }
+                if (vd_out) {
+                    vd_out[3 * o] = vx;
+                    vd_out[3 * o + 1] = vy;
+                    vd_out[3 * o + 2] = vz;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace nr
 
 using namespace nr;
@@ -231,6 +424,13 @@ int nr_sample_pdf(const float* bins, const float* weights, const float* u, int B
                   nr_stream_t stream) {
     NR_REQUIRE(bins && weights && samples && B >= 0 && Nb >= 2 && Ns > 0, "nr_sample_pdf: bad arguments");
     if (B == 0) return NR_OK;
+    if (Nb > 64 * kMaxPerLane + 1) {  // long rays: one workgroup per ray
+        NR_REQUIRE(Nb <= kLongMaxBins, "nr_sample_pdf: Nb=%d exceeds %d", Nb, kLongMaxBins);
+        hipLaunchKernelGGL(sample_pdf_long_kernel, dim3(B), dim3(kLongThreads), sizeof(float) * 3 * Nb,
+                           static_cast<hipStream_t>(stream), bins, weights, u, Nb, Ns, samples);
+        NR_LAUNCH_CHECK("nr_sample_pdf");
+        return NR_OK;
+    }
     const size_t lds = sizeof(float) * kRaysPerBlock * 3 * Nb;
     NR_REQUIRE(lds <= 64 * 1024 && Nb - 1 <= 512, "nr_sample_pdf: Nb=%d too large", Nb);
     hipLaunchKernelGGL(sample_pdf_kernel, dim3(ceil_div(B, kRaysPerBlock)), dim3(64 * kRaysPerBlock), lds,
@@ -243,6 +443,17 @@ int nr_sample_hierarchical(const float* ro, const float* rd, const float* zc, co
                            int B, int Nc, int Nf, float* zf, float* pts, float* viewdirs, nr_stream_t stream) {
     NR_REQUIRE(zc && wc && zf && B >= 0 && Nc >= 3 && Nf > 0 && (!pts || (ro && rd)) && (!viewdirs || rd),
                "nr_sample_hierarchical: bad arguments");
+    if (Nc + Nf > 64 * kMaxPerLane) {  // long rays: one workgroup per ray, sorted in runs of 512
+        NR_REQUIRE(Nc + Nf <= kLongMaxT, "nr_sample_hierarchical: Nc+Nf=%d exceeds %d", Nc + Nf, kLongMaxT);
+        if (B == 0) return NR_OK;
+        const size_t lds_long = sizeof(float) * (3 * (Nc - 1) + ceil_div(Nc + Nf, kRun) * kRun);
+        NR_REQUIRE(lds_long + sizeof(float) * (kLongThreads / 64) <= 64 * 1024,
+                   "nr_sample_hierarchical: Nc=%d Nf=%d need %zu bytes of LDS", Nc, Nf, lds_long);
+        hipLaunchKernelGGL(sample_hier_long_kernel, dim3(B), dim3(kLongThreads), lds_long,
+                           static_cast<hipStream_t>(stream), ro, rd, zc, wc, u, Nc, Nf, zf, pts, viewdirs);
+        NR_LAUNCH_CHECK("nr_sample_hierarchical");
+        return NR_OK;
+    }
     NR_REQUIRE(Nc + Nf <= 64 * kMaxPerLane, "nr_sample_hierarchical: Nc+Nf=%d exceeds %d", Nc + Nf,
                64 * kMaxPerLane);
     if (B == 0) return NR_OK;

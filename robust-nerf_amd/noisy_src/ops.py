@@ -158,6 +158,8 @@ def stratified_sample(rays_o, rays_d, near, far, num_samples, t_rand=None, lindi
 
 
 def sample_pdf(bins, weights, num_samples, u=None):
+    """Inverse-CDF samples (..., num_samples) in the order of ``u``; u None -> det.  At most
+    4097 bins per ray (RuntimeError above)."""
     _check(bins, weights, u)
     b, w = _c(bins.detach()), _c(weights.detach())
     lead = b.shape[:-1]
@@ -198,7 +200,8 @@ class _Hierarchical(torch.autograd.Function):
 def sample_hierarchical(rays_o, rays_d, z_coarse, w_coarse, num_samples_fine, u=None, viewdirs=False):
     """Returns (pts_fine (B,Nc+Nf,3), z_fine (B,Nc+Nf)) -- and with ``viewdirs`` the
     normalised directions per sample from the same launch; u None -> det.  The fine
-    depths are detached as in the reference (rays.py:325)."""
+    depths are detached as in the reference (rays.py:325).  Nc + Nf <= 4096 (RuntimeError
+    above); the coarse depths may come in any order."""
     _check(rays_o, rays_d, z_coarse, w_coarse, u)
     return _Hierarchical.apply(rays_o, rays_d, z_coarse.detach(), w_coarse.detach(),
                                u.detach() if u is not None else None, num_samples_fine, bool(viewdirs))

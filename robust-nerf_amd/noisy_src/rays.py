@@ -65,7 +65,7 @@ def sample_along_rays(rays_o: torch.Tensor, rays_d: torch.Tensor, near: float, f
 
 def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, num_samples: int, det: bool = False,
                u: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Reference rays.py:213-279 -> samples (..., num_samples)."""
+    """Reference rays.py:213-279 -> samples (..., num_samples).  Up to 4097 bins per ray."""
     if not det and u is None:
         u = torch.rand(*bins.shape[:-1], num_samples, device=weights.device)
     return ops.sample_pdf(bins, weights, num_samples, u=None if det else u)
@@ -74,7 +74,8 @@ def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, num_samples: int, det:
 def sample_hierarchical(rays_o: torch.Tensor, rays_d: torch.Tensor, z_vals: torch.Tensor, weights: torch.Tensor,
                         num_samples_fine: int, det: bool = False,
                         u: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Reference rays.py:282-333 -> (pts_fine (..., Nc+Nf, 3), z_vals_fine (..., Nc+Nf)), sorted."""
+    """Reference rays.py:282-333 -> (pts_fine (..., Nc+Nf, 3), z_vals_fine (..., Nc+Nf)), sorted.
+    Nc + Nf <= 4096."""
     batch_shape = rays_o.shape[:-1]
     Nc = z_vals.shape[-1]
     if not det and u is None:
