@@ -124,6 +124,19 @@ int nr_gather_rays(const int64_t* idx, int64_t n_rays, int B,
                    float* out_o, float* out_d, float* out_rgb, int* bad_index,
                    nr_stream_t stream);
 
+/* ---- batch assembly: PixelSampler.sample_batch  (noisy_src/data_pose_opt.py:178-198)
+ * For the flat pixel index idx[b] into images (n_img,H,W,3): out_img[b] =
+ * idx / (H*W), out_pix[b] = (u, v) = (idx % W, (idx % (H*W)) / W) as fp32,
+ * out_rgb[b] = images[idx] -- the reference's image_indices / pixel_coords /
+ * target_rgb tables without the two n_pixels-long tables.  64-bit index
+ * arithmetic (n_img*H*W may exceed 2^31).  idx outside [0, n_img*H*W) gives
+ * NaN pix / rgb rows and out_img = -1 and, in the validating mode (bad_index
+ * non-NULL, caller-zeroed device int), sets *bad_index = 1.                  */
+int nr_gather_pixels(const int64_t* idx, int n_img, int H, int W,
+                     const float* images, int B, int64_t* out_img,
+                     float* out_pix, float* out_rgb, int* bad_index,
+                     nr_stream_t stream);
+
 /* ---- A5: sample_along_rays  (noisy_src/rays.py:145-210) ------------------
  * z (B,N); pts (B,N,3) nullable.  t_rand (B,N) nullable -> no perturbation.
  * viewdirs (B*N,3) nullable: rays_d / |rays_d| per sample (rendering.py:165), as

@@ -376,6 +376,24 @@ __global__ void gather_rays_kernel(const int64_t* idx, int64_t n_rays, int B, co
     }
 }
 
+// PixelSampler.sample_batch (data_pose_opt.py:178-198): flat pixel index ->
+// (image, (u, v), colour).  The reference's image_indices / pixel_coords tables
+// are pure functions of the index, so only the images are read.  64-bit index
+// arithmetic throughout: n_img * H * W may exceed 2^31.
+__global__ void gather_pixels_kernel(const int64_t* idx, int64_t n_pixels, int64_t hw, int64_t W, const float* images,
+                                     int B, int64_t* out_img, float* out_pix, float* out_rgb, int* bad_index) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t i = idx[b];
+    const bool ok = i >= 0 && i < n_pixels;
+    if (!ok && bad_index) *bad_index = 1;  // validating mode: the host wrapper raises IndexError
+    const float nan = __builtin_nanf("");
+    out_img[b] = ok ? i / hw : -1;
+    out_pix[2 * b + 0] = ok ? static_cast<float>(i % W) : nan;         // u (hw is a multiple of W)
+    out_pix[2 * b + 1] = ok ? static_cast<float>((i % hw) / W) : nan;  // v
+    for (int c = 0; c < 3; ++c) out_rgb[3 * b + c] = ok ? images[3 * i + c] : nan;
+}
+
 // ---------------------------------------------------------------- A5 -----
 __global__ void stratified_kernel(const float* ro, const float* rd, const float* t_rand, float near_,
                                   float far_, int lindisp, int B, int N, float* z_out, float* pts, float* vd) {
@@ -617,6 +635,18 @@ int nr_gather_rays(const int64_t* idx, int64_t n_rays, int B, const float* rays_
     hipLaunchKernelGGL(gather_rays_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), idx,
                        n_rays, B, rays_o, rays_d, colors, out_o, out_d, out_rgb, bad_index);
     NR_LAUNCH_CHECK("nr_gather_rays");
+    return NR_OK;
+}
+
+int nr_gather_pixels(const int64_t* idx, int n_img, int H, int W, const float* images, int B, int64_t* out_img,
+                     float* out_pix, float* out_rgb, int* bad_index, nr_stream_t stream) {
+    NR_REQUIRE(idx && images && out_img && out_pix && out_rgb && B >= 0 && n_img >= 0 && H > 0 && W > 0,
+               "nr_gather_pixels: bad arguments");
+    if (B == 0) return NR_OK;
+    const int64_t hw = static_cast<int64_t>(H) * W;
+    hipLaunchKernelGGL(gather_pixels_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), idx,
+                       n_img * hw, hw, static_cast<int64_t>(W), images, B, out_img, out_pix, out_rgb, bad_index);
+    NR_LAUNCH_CHECK("nr_gather_pixels");
     return NR_OK;
 }
 

@@ -7,13 +7,15 @@ Python loop over the unique images of the batch, two ``.item()`` syncs per image
 masked scatters (data_pose_opt.py:83-148).  Here one HIP kernel
 (``nr_rays_from_pixels_fwd``) gathers every ray straight from (image, u, v) and its
 image's pose, and its backward scatters dL/d(rays_o, rays_d) into dL/d(poses): same
-values, same gradient, no host round trips.
+values, same gradient, no host round trips.  Batch assembly is one kernel too
+(``nr_gather_pixels``): image index, pixel coordinates and colour from the drawn flat
+pixel index, without the reference's two n_pixels-long index tables.
 """
 
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -43,16 +45,35 @@ class PixelDataset:
     def __init__(self, data: BlenderData):
         self.H, self.W, self.focal = data.H, data.W, data.focal
         self.device = data.images.device
-        n_img = data.images.shape[0]
-        hw = self.H * self.W
-        v, u = torch.meshgrid(torch.arange(self.H, dtype=torch.float32, device=self.device),
-                              torch.arange(self.W, dtype=torch.float32, device=self.device), indexing="ij")
-        single = torch.stack([u.flatten(), v.flatten()], dim=-1)
-        self.image_indices = torch.repeat_interleave(torch.arange(n_img, dtype=torch.long, device=self.device), hw)
-        self.pixel_coords = single.unsqueeze(0).expand(n_img, -1, -1).reshape(-1, 2)
-        self.target_rgb = data.images.reshape(-1, 3)
-        self.n_pixels = n_img * hw
+        self.n_images = data.images.shape[0]
+        # (n_img, H, W, 3) fp32, contiguous: what ``ops.gather_pixels`` reads
+        self.images = data.images.float().contiguous()
+        self.target_rgb = self.images.reshape(-1, 3)
+        self.n_pixels = self.n_images * self.H * self.W
         self.ray_directions = ops.ray_directions(self.H, self.W, self.focal, self.W / 2.0, self.H / 2.0, self.device)
+        # the reference's two n_pixels-long tables (data_pose_opt.py:52-70) are pure functions
+        # of the index (16 B per pixel: 1 GB at 100 views of 800 x 800); the sampler computes
+        # them per batch in its gather kernel, and the attributes are built on first access
+        self._image_indices: Optional[torch.Tensor] = None
+        self._pixel_coords: Optional[torch.Tensor] = None
+
+    @property
+    def image_indices(self) -> torch.Tensor:
+        """(n_pixels,) int64: the image of every pixel (built on first access)."""
+        if self._image_indices is None:
+            self._image_indices = torch.repeat_interleave(
+                torch.arange(self.n_images, dtype=torch.long, device=self.device), self.H * self.W)
+        return self._image_indices
+
+    @property
+    def pixel_coords(self) -> torch.Tensor:
+        """(n_pixels, 2) fp32 (u, v) of every pixel (built on first access)."""
+        if self._pixel_coords is None:
+            v, u = torch.meshgrid(torch.arange(self.H, dtype=torch.float32, device=self.device),
+                                  torch.arange(self.W, dtype=torch.float32, device=self.device), indexing="ij")
+            single = torch.stack([u.flatten(), v.flatten()], dim=-1)
+            self._pixel_coords = single.unsqueeze(0).expand(self.n_images, -1, -1).reshape(-1, 2)
+        return self._pixel_coords
 
     def get_rays_from_pixels(self, pixel_batch: PixelBatch, poses: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference data_pose_opt.py:83-148.  ``poses`` holds one pose per UNIQUE image of
@@ -73,13 +94,16 @@ class PixelSampler:
         self.device = dataset.device
         self.n_pixels = dataset.n_pixels
 
-    def sample_batch(self, generator=None) -> PixelBatch:
+    def sample_batch(self, generator=None, out=None) -> PixelBatch:
         """``generator`` (optional, on the dataset's device) makes the draw reproducible
-        across data-parallel ranks that each take a slice of it."""
+        across data-parallel ranks that each take a slice of it.  One kernel
+        (``nr_gather_pixels``) turns the drawn indices into the batch: the values of the
+        reference's three table gathers, bit for bit.  ``out``: preallocated
+        (image_indices, pixel_coords, target_rgb) tensors the kernel writes in place (the
+        static inputs of ``engine.GraphedPoseTrainer``); the batch then holds them."""
         idx = torch.randint(0, self.n_pixels, (self.batch_size,), device=self.device, generator=generator)
-        ds = self.dataset
-        return PixelBatch(image_indices=ds.image_indices[idx], pixel_coords=ds.pixel_coords[idx],
-                          target_rgb=ds.target_rgb[idx], in_range=True)
+        img, pix, rgb = ops.gather_pixels(idx, self.dataset.images, validate=False, out=out)
+        return PixelBatch(image_indices=img, pixel_coords=pix, target_rgb=rgb, in_range=True)
 
     def get_rays_for_batch(self, pixel_batch: PixelBatch, poses: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference data_pose_opt.py:200-223 with ``poses`` = every image's pose (N,4,4):

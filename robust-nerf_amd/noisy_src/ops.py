@@ -104,6 +104,37 @@ def gather_rays(idx, rays_o, rays_d, colors, validate: bool = False):
     return out
 
 
+def gather_pixels(idx, images, validate: bool = False, out=None):
+    """PixelSampler batch assembly (data_pose_opt.py:178-198): for the flat pixel indices
+    ``idx`` into ``images`` (n_img, H, W, 3) the image index (B,) int64, the pixel
+    coordinates (B, 2) fp32 (u, v) and the colours (B, 3), in one kernel and without the
+    reference's two n_pixels-long tables.  ``out``: that triple preallocated (contiguous,
+    on the images' device), written in place (static buffers of a graph replay).
+    ``validate`` raises IndexError for indices outside the images (one host read)."""
+    _check(idx, images)
+    if images.dim() != 4 or images.shape[-1] != 3 or images.dtype != _f32 or not images.is_contiguous():
+        raise ValueError("gather_pixels: images must be a contiguous fp32 (n_img, H, W, 3) tensor")
+    i = idx.to(torch.int64).contiguous()
+    B = i.shape[0]
+    n_img, H, W = images.shape[:3]
+    if out is None:
+        out = (torch.empty(B, device=i.device, dtype=torch.int64), torch.empty(B, 2, device=i.device, dtype=_f32),
+               torch.empty(B, 3, device=i.device, dtype=_f32))
+    else:
+        out = tuple(out)
+        _check(*out)
+        want = ((B,), torch.int64), ((B, 2), _f32), ((B, 3), _f32)
+        if len(out) != 3 or any(tuple(t.shape) != s or t.dtype != d or t.device != i.device or not t.is_contiguous()
+                                for t, (s, d) in zip(out, want)):
+            raise ValueError(f"gather_pixels: out must be contiguous int64 ({B},), fp32 ({B}, 2), fp32 ({B}, 3) "
+                             "tensors on the index's device")
+    flag = torch.zeros(1, device=i.device, dtype=torch.int32) if validate else None
+    call("nr_gather_pixels", ptr(i), n_img, H, W, ptr(images), B, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(flag),
+         _stream())
+    _raise_if_flagged(flag, n_img * H * W, "pixel index")
+    return out
+
+
 # ---------------------------------------------------------------- A5 / A9 / A10
 def _pts_bwd(ctx, g_pts, z):
     """pts = o + d * z (rays.py:208 / :331): sum the sample gradients per ray."""

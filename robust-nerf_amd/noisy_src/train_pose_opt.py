@@ -19,6 +19,10 @@ Joint NeRF + camera-pose training step — drop-in for ShawnnnLiu/Robust-NeRF
   ``summary.json``.  The step is ``engine.PoseTrainer`` (HIP, no host syncs).  Under
   ``torchrun`` it is data parallel exactly like ``train.train``: identical global draws
   on every rank, contiguous slices, network and pose gradients averaged over RCCL.
+  ``graph=True`` (``--graph``) replays the step from hipGraphs after iteration 0
+  (``engine.GraphedPoseTrainer``: one graph for frozen poses, one for optimising, the
+  pixel batch gathered straight into their static inputs), bit-identical to eager; it
+  pays below 1,024 rays per GPU.
 """
 
 from __future__ import annotations
@@ -40,7 +44,8 @@ from .config import RenderConfig
 from .config import NeRFConfig
 from .data import BlenderData, load_blender_data
 from .data_pose_opt import PixelBatch, PixelSampler, create_pixel_dataset
-from .engine import LaggedScalars, PoseTrainer, check_run_args, init_distributed, mean_over_ranks, rank_slice
+from .engine import (GraphedPoseTrainer, LaggedScalars, PoseTrainer, check_run_args, init_distributed,
+                     mean_over_ranks, rank_slice)
 from .logger import ExperimentLogger, TrainingMetrics, ValidationMetrics
 from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim
 from .model import NeRF
@@ -273,15 +278,24 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                  rotation_reg_weight: float = 0.01, translation_reg_weight: float = 0.001, *,
                                  train_data: Optional[BlenderData] = None, val_data: Optional[BlenderData] = None,
                                  process_group=None, experiment_name: Optional[str] = None,
-                                 log=print) -> Dict[str, object]:
+                                 log=print, graph: bool = False) -> Dict[str, object]:
     """Reference train_pose_opt.py:613-1054 (same arguments, outputs and files).
     ``train_data`` / ``val_data`` (optional) replace the on-disk scene; ``process_group``
-    makes it data parallel; ``experiment_name`` pins the generated run name (all ranks)."""
+    makes it data parallel; ``experiment_name`` pins the generated run name (all ranks).
+    ``graph`` replays the step from hipGraphs (``engine.GraphedPoseTrainer``; same results
+    as eager): iteration 0 runs eagerly, the frozen-pose graph is captured at the next
+    iteration; the first iteration that optimises the poses runs eagerly (it creates the
+    pose Adam's state) and the optimising graph is captured at the one after it.  With
+    data parallelism it needs the nccl backend."""
     import torch.distributed as dist
 
     rank, world = 0, 1
     if process_group is not None:
         rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
+    if graph and world > 1 and dist.get_backend(process_group) != "nccl":
+        # the captured step contains the all-reduces: only RCCL collectives are graph-capturable
+        raise ValueError("train_with_pose_optimization(graph=True) with data parallelism needs the nccl (RCCL) "
+                         "backend")
     check_run_args(config, world, train_data, val_data)
     set_seed(config.train.seed)
     device = config.train.device
@@ -343,6 +357,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     best_psnr = 0.0
     lagged = LaggedScalars()  # logged losses read one iteration late: no per-step host sync
     t_prev = time.time()
+    graphed = None
 
     def log_iteration(done):
         if done is None or logger is None:
@@ -360,13 +375,22 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                 f"time: {(time.time() - start) / 60:.1f}min")
 
     for iteration in range(config.train.num_iterations):
-        batch = pixel_sampler.sample_batch()  # the global batch, identical on every rank
+        # the global batch, identical on every rank (one process in graph mode: the gather
+        # kernel writes it straight into the graphs' static inputs).  The draws stay in the
+        # eager order: randint, rand, rand
+        batch = pixel_sampler.sample_batch(out=graphed.static if (graphed is not None and world == 1) else None)
         now = iteration >= pose_opt_delay
         t_rand = torch.rand(B, rc.num_samples, device=device) if rc.perturb else None
         u = torch.rand(B, rc.num_samples_fine, device=device) if (rc.use_hierarchical and model_fine) else None
         sl = rank_slice(B, rank, world) if world > 1 else slice(0, B)
-        m = trainer.step(batch.slice(sl) if world > 1 else batch, optimize_poses=now,
-                         t_rand=None if t_rand is None else t_rand[sl], u=None if u is None else u[sl])
+        args = (batch.slice(sl) if world > 1 else batch, now, None if t_rand is None else t_rand[sl],
+                None if u is None else u[sl])
+        if graph and iteration >= 1:
+            if graphed is None:  # after one eager step: the networks' Adam state exists
+                graphed = GraphedPoseTrainer(trainer, args[0], args[2], args[3], warmup=0)
+            m = graphed.step(*args)  # eager once more where the pose Adam's state is new
+        else:
+            m = trainer.step(*args)
         keys = ["loss", "loss_coarse"] + (["loss_fine"] if "loss_fine" in m else [])
         t_now = time.time()
         log_iteration(lagged.push(mean_over_ranks([m[k] for k in keys], process_group),
@@ -432,8 +456,16 @@ def create_nerf_for(config: NeRFConfig, device):
     return mc, mf
 
 
+# what the measured table shows (profiles/pose_graph_ab.json)
+GRAPH_HELP = ("replay the joint step from hipGraphs, one for frozen poses and one for optimising (same results as "
+              "eager; with RCCL data parallelism the all-reduces are captured too). Measured on one MI355X, bf16 "
+              "64c+128f, ms per step eager -> replayed: 512 rays 1.55 -> 1.04; 1024 rays (the default batch) "
+              "1.56 -> 1.55, no gain; 4096 rays 5.20 -> 5.22, 0.4 %% slower. It pays below 1024 rays per GPU")
+
+
 def build_arg_parser():
-    """Reference train_pose_opt.py:1057-1142 flags (same names and defaults) plus ``--precision``."""
+    """Reference train_pose_opt.py:1057-1142 flags (same names and defaults) plus ``--precision``
+    and ``--graph``."""
     import argparse
     ap = argparse.ArgumentParser(description="Joint NeRF + camera pose optimisation (MI355X HIP path)")
     ap.add_argument("--scene", type=str, default="lego")
@@ -464,6 +496,7 @@ def build_arg_parser():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
                     help="MLP operand precision (fp32 = the reference's numerics)")
+    ap.add_argument("--graph", action="store_true", help=GRAPH_HELP)
     return ap
 
 
@@ -491,7 +524,8 @@ def main(argv=None) -> None:
         dist.broadcast_object_list(name, src=0, group=pg)
     train_with_pose_optimization(cfg, noise_config, a.init_mode, a.pose_lr, a.pose_opt_delay,
                                  not a.no_learn_rotation, not a.no_learn_translation, a.rotation_reg_weight,
-                                 a.translation_reg_weight, process_group=pg, experiment_name=name[0])
+                                 a.translation_reg_weight, process_group=pg, experiment_name=name[0],
+                                 graph=a.graph)
     if pg is not None:
         import torch.distributed as dist
         dist.destroy_process_group()
