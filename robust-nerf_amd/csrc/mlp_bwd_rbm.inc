@@ -1,5 +1,6 @@
 // 16-bit (bf16 / fp16) backward dX chain of the fused MLP, ROW-BLOCK MAJOR
-// (included by mlp.hip after mlp_fwd_rbm.inc, whose stream and layer loop it reuses).
+// (included by mlp_16.hip after mlp_fwd_rbm.inc, whose stream and layer loop it reuses;
+// BwdrArgs: mlp_launch.hpp).
 // Reference: the autograd backward of noisy_src/model.py:145-196.
 //
 //   dz_heads = [g_sigma * (sigma > 0), g_rgb * (1 - rgb) * rgb]        (VALU)
@@ -14,34 +15,9 @@
 // row block's accumulator (32 input features x 32 samples) is final after its
 // 2 * NB_out MFMAs and its epilogue (sigma term, ReLU mask, 16-bit pack, store)
 // runs under the next row block's MFMAs.  Same products in the same k order as
-// the chunk-major mlp_bwd_kernel, so the dz images are bit-identical to it.
+// the chunk-major 16-bit chain it replaced, to which its dz images were bit-identical.
 // The ReLU masks of every layer are staged into LDS once (LDS-DMA, 1 KB per
 // layer and wave), so no global load waits inside the stream.
-
-struct BwdrArgs {
-    float gscale;
-    const char* packed;
-    const float* rgb;
-    const float* sigma;
-    const float* g_rgb;
-    const float* g_sigma;
-    const char* saved;
-    char* ws;
-    int64_t M, tiles;
-    const uint8_t* flags;   // active tiles (tile_flags_kernel) and their 64-tile block counts
-    const uint32_t* blk_count;
-    int64_t nseg;
-    uint32_t* dw_list;      // the dW kernel's list and count (place_segment)
-    uint32_t* count;
-    int64_t scratch_base;   // first of the kScratchTiles tiles waves without an active tile run on
-    int n_layers;
-    int64_t base;        // pk_bwdr of the dir layer: the stream's first chunk
-    int64_t vrgb, vhead;
-    int64_t mask_off;
-    int n_mask;
-    int64_t ws_off[kMaxTrunk + 3];
-    int ws_feat, ws_dir, ws_heads;
-};
 
 constexpr int kBwdrSlot = 32 * 1024;  // every dX-chain chunk: 2 row blocks x 8 k blocks, or 4 x 4
 __host__ __device__ constexpr int bwdr_mask_off() { return 2 * kBwdrSlot; }

@@ -1,4 +1,5 @@
-// 16-bit (bf16 / fp16) forward of the fused MLP, ROW-BLOCK MAJOR (included by mlp.hip).
+// 16-bit (bf16 / fp16) forward of the fused MLP, ROW-BLOCK MAJOR (included by mlp_16.hip;
+// RbmArgs: mlp_launch.hpp).
 // Reference: noisy_src/model.py:145-196 (NeRF.forward), 20-80 (PositionalEncoding).
 //
 // Each wave owns one 32-sample tile.  A layer's packed image is row-block major:
@@ -11,8 +12,8 @@
 // The layer input h_{i-1} and the output h_i being built both stay in registers
 // (8 blocks = 64 VGPRs each, ping-pong over pairs of layers); LDS holds only the
 // weight ring (two 42-KB slots).  Same operands, same per-row-block accumulation
-// order (k ascending) and the same epilogue arithmetic as the chunk-major kernel,
-// so the results are bit-identical to it.
+// order (k ascending) and the same epilogue arithmetic as the chunk-major 16-bit
+// kernel it replaced, to which its results were bit-identical.
 //
 // Stream protocol (two slots): at the boundary of chunk q every wave waits for its
 // own LDS-DMA pieces of chunk q (a counted vmcnt: the saved-activation stores it
@@ -28,25 +29,6 @@ constexpr int kRbmWaves = 8;
 __host__ __device__ constexpr int rbm_xenc_off() { return 2 * kRbmSlot; }
 __host__ __device__ constexpr int rbm_head_off(int XB, int W) { return 2 * kRbmSlot + W * XB * 2 * kFragBytes; }
 __host__ __device__ constexpr int rbm_lds_bytes(int XB, int W) { return rbm_head_off(XB, W) + 3 * 1024; }
-
-struct RbmArgs {
-    const char* packed;
-    const float* params;
-    const float* x;
-    const float* d;
-    float* rgb;
-    float* sigma;
-    char* saved;
-    int64_t M, tiles;
-    int L, Ld, n_layers;
-    uint32_t skips;
-    int64_t base;  // byte offset of layer 0's row-block-major image in packed
-    int64_t vhead, sig_b, rgb_b;
-    int64_t sv_off[kMaxTrunk + 4];
-    int sv_feat, sv_denc, sv_hc;
-    int64_t mask_off;
-    int n_mask;
-};
 
 struct RStream {
     char* lds;
@@ -97,16 +79,6 @@ __device__ __forceinline__ void rbm_boundary(RStream& s, int next_ckb) {
 template <int OFF>
 __device__ __forceinline__ void rbm_dsr(bf16x8& d, uint32_t a) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(a), "i"(OFF));
-}
-
-// compile-time loop: f(integral_constant<int, j>) for j = 0..NN-1
-template <int... Js, class F>
-__device__ __forceinline__ void rbm_static_for(std::integer_sequence<int, Js...>, F&& f) {
-    (f(std::integral_constant<int, Js>{}), ...);
-}
-template <int NN, class F>
-__device__ __forceinline__ void rbm_static_for(F&& f) {
-    rbm_static_for(std::make_integer_sequence<int, NN>{}, f);
 }
 
 // s_waitcnt lgkmcnt(N) tied to the registers it publishes

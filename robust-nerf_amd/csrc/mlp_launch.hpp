@@ -1,0 +1,219 @@
+// Between mlp.hip (the extern "C" entry points, which fill these argument structs from
+// the plan) and the translation units that hold the kernels and launch them.
+#pragma once
+
+#include "common.hpp"
+#include "mlp_plan.hpp"
+#include "optim.hpp"
+
+#pragma GCC visibility push(hidden)  // the launchers are internal to the library
+namespace nr {
+
+// fp16 backward runs on dz scaled by 2^14 (the per-sample gradients of a mean
+// loss over 4096 rays sit near 1e-6, in fp16's subnormal range); the dW reduce and
+// the input gradients divide it out exactly.
+inline float grad_scale(int prec) { return prec == NR_PREC_FP16 ? 16384.0f : 1.0f; }
+
+// ------------------------------------------- fp32, chunk-major (mlp_fp32.hip) ----
+// The weight stream: a sequence of chunks (all row blocks of one k block of one layer
+// image) consumed in order.
+constexpr int kMaxChunks = 176;  // >= sum of KB (forward) or NB (backward) over the MFMA layers
+
+struct StreamDesc {
+    int64_t base;                  // byte offset of the stream's first chunk in `packed`
+    int nq;                        // chunks
+    int ckb[kMaxChunks];           // bytes loaded per chunk, in KB
+    int cadv[kMaxChunks];          // bytes to the next chunk, in KB (>= ckb: a chunk may be loaded in part)
+};
+
+struct FwdArgs {
+    const char* packed;
+    const float* params;
+    const float* x;
+    const float* d;
+    float* rgb;
+    float* sigma;
+    char* saved;
+    int64_t M, tiles;
+    int L, Ld, n_layers;
+    uint32_t skips;
+    int slot_bytes;
+    StreamDesc sd;  // W images: trunk 0..n-1, feat, dir
+    int64_t vb[kMaxMfmaLayers];
+    int64_t bo[kMaxMfmaLayers];  // bias offsets in params (not read: the kernel takes biases from the vb images)
+    int64_t vsig, vrgb, sig_b, rgb_b;
+    int64_t sv_off[kMaxTrunk + 4];
+    int sv_feat, sv_denc, sv_hc;
+    int64_t mask_off;
+    int n_mask;
+};
+
+struct BwdArgs {
+    float gscale, inv_gscale;  // loss scale applied to dL/d(rgb, sigma) and divided out of g_x / g_d (fp32: 1)
+    const char* packed;
+    const float* params;
+    const float* x;
+    const float* d;
+    const float* rgb;
+    const float* sigma;
+    const float* g_rgb;
+    const float* g_sigma;
+    float* g_x;
+    float* g_d;
+    const char* saved;
+    char* ws;
+    int64_t M, tiles;
+    const uint8_t* flags;       // active tiles (tile_flags_kernel) and their 64-tile block counts
+    const uint32_t* blk_count;
+    int64_t nseg;
+    uint32_t* dw_list;          // the dW kernel's list and count (place_segment)
+    uint32_t* count;
+    int L, Ld, n_layers;
+    uint32_t skips;
+    int slot_bytes;
+    StreamDesc sd;  // W^T images: dir, feat, trunk n-1..1 [, trunk 0 when g_x/g_d]
+    int64_t vsig, vrgb;
+    int64_t mask_off;
+    int n_mask;
+    int64_t ws_off[kMaxTrunk + 3];
+    int ws_feat, ws_dir, ws_heads;
+};
+
+// train: save the activations; want_x: also compute g_x / g_d.  Both set a.slot_bytes.
+int launch_fwd(const MlpPlan& p, FwdArgs& a, bool train, hipStream_t s);
+int launch_bwd(const MlpPlan& p, BwdArgs& a, bool want_x, hipStream_t s);
+
+// ------------------------------------- 16-bit, row-block major (mlp_16.hip) ----
+struct RbmArgs {
+    const char* packed;
+    const float* params;
+    const float* x;
+    const float* d;
+    float* rgb;
+    float* sigma;
+    char* saved;
+    int64_t M, tiles;
+    int L, Ld, n_layers;
+    uint32_t skips;
+    int64_t base;  // byte offset of layer 0's row-block-major image in packed
+    int64_t vhead, sig_b, rgb_b;
+    int64_t sv_off[kMaxTrunk + 4];
+    int sv_feat, sv_denc, sv_hc;
+    int64_t mask_off;
+    int n_mask;
+};
+
+struct BwdrArgs {
+    float gscale;
+    const char* packed;
+    const float* rgb;
+    const float* sigma;
+    const float* g_rgb;
+    const float* g_sigma;
+    const char* saved;
+    char* ws;
+    int64_t M, tiles;
+    const uint8_t* flags;   // active tiles (tile_flags_kernel) and their 64-tile block counts
+    const uint32_t* blk_count;
+    int64_t nseg;
+    uint32_t* dw_list;      // the dW kernel's list and count (place_segment)
+    uint32_t* count;
+    int64_t scratch_base;   // first of the kScratchTiles tiles waves without an active tile run on
+    int n_layers;
+    int64_t base;        // pk_bwdr of the dir layer: the stream's first chunk
+    int64_t vrgb, vhead;
+    int64_t mask_off;
+    int n_mask;
+    int64_t ws_off[kMaxTrunk + 3];
+    int ws_feat, ws_dir, ws_heads;
+};
+
+int launch_fwd_rbm(const MlpPlan& p, const RbmArgs& a, bool train, hipStream_t s);
+int launch_bwd_rbm(const MlpPlan& p, const BwdrArgs& a, hipStream_t s);
+// g_x / g_d from the dz images the dX chain stored (mlp_dinput_kernel)
+int input_grads16(const MlpPlan& p, const MlpSizes& z, const char* packed, const float* x, const float* d, float* g_x,
+                  float* g_d, const char* ws, int64_t M, hipStream_t s);
+
+// --------------------------------------- active tiles, dW, reduce (mlp_dw.hip) ----
+#ifndef NR_DW_NSTAGE
+#define NR_DW_NSTAGE 4  // LDS staging ring depth of the dW kernel (tiles)
+#endif
+constexpr int kDwThreads = 512;
+constexpr int kDwWaves = kDwThreads / 64;
+static_assert(kDwWaves == kDwMaxWaves, "dW wave shares are planned for 8-wave workgroups");
+
+constexpr int kDwMaxWgs = 256;  // one round of workgroups (make_sizes: NR_DW_WGS)
+struct DwArgs {
+    float* slabs;
+    int njobs;
+    int64_t tiles;
+    const uint32_t* list;           // active tiles in order and their count (built during the dX launch)
+    const uint32_t* count;
+    int list_lds;                   // LDS byte offset the chunk's list entries are staged to (0: read them global)
+    int job_chunks[kMaxJobs];       // chunks of each job: list entries split evenly in order
+    uint16_t wg_map[kDwMaxWgs];     // workgroup -> job | chunk << 5 (chunk-major: one chunk of every job in a row)
+    int stage_bytes, nstage;
+    int64_t slab_floats_per_chunk;
+    int job_NBz[kMaxJobs], job_KB[kMaxJobs];
+    int64_t job_slab[kMaxJobs];
+    const char* seg_ptr[kMaxJobs][2 * kMaxJobSeg];  // tensor region: dz segments, then inputs
+    uint8_t seg_blocks[kMaxJobs][2 * kMaxJobSeg];
+    // wave share (DwWave) packed: row0 | np << 6 | col0 << 9 | nq << 15 | bias << 17; 0 = idle
+    int job_wave[kMaxJobs][kDwWaves];
+};
+static_assert(sizeof(DwArgs) <= 4096, "dW kernel arguments exceed 4 KiB");
+
+__host__ __device__ constexpr int dw_wave_pack(int row0, int np, int col0, int nq, int bias) {
+    return row0 | np << 6 | col0 << 9 | nq << 15 | bias << 17;
+}
+
+// g_params[param] = sum over chunks of its slab entry (fixed chunk order: deterministic).
+struct ReduceArgs {
+    const float* slabs;
+    float* g;
+    float inv_gscale;  // fp16: undo the backward's loss scale (a power of two: exact)
+    int64_t param_count;
+    int64_t slab_floats_per_chunk;
+    int n_red;
+    int rows[kMaxRed], in[kMaxRed], nseg[kMaxRed], bjob[kMaxRed], brow0[kMaxRed];
+    int64_t w_off[kMaxRed], b_off[kMaxRed];
+    RedSeg seg[kMaxRed][kMaxSeg];
+    int64_t job_slab[kMaxJobs];
+    int job_KB[kMaxJobs];
+    int job_chunks[kMaxJobs];  // slab sets of each job, summed in chunk order
+};
+
+int launch_tile_flags(const float* g_rgb, const float* g_sigma, int64_t M, int dense, int64_t nseg, uint8_t* flags,
+                      uint32_t* blk_count, hipStream_t s);
+int launch_dw(int prec, const DwArgs& a, int nwg, size_t lds, hipStream_t s);
+int launch_dw_reduce(const ReduceArgs& a, int max_rows, hipStream_t s);
+
+// ------------------------------------ pack, fused optimizer step (mlp_pack.hip) ----
+// Destination table of the fused optimizer step (see mlp_pack.hip)
+constexpr int kPackSlots = 3;
+constexpr int64_t kDstMaxOff = int64_t(1) << 29;
+struct PackIdx {
+    uint32_t* table;
+    int64_t n;  // flat parameters
+};
+
+struct AdamSpanDev {
+    float *p, *g, *m, *v;
+    int64_t n;
+    const float* partials;
+    float max_norm;
+    const uint32_t* table;
+    char* packed;
+};
+struct AdamMultiArgs {
+    AdamSpanDev s[kMaxAdamSpans];
+    float omb1, b2, omb2, eps, step_size, bc2_sqrt;
+    const float* sched;  // nullable: {step_size, bc2_sqrt} read on the device (graph replay)
+};
+
+// nr_mlp_pack's four kernels; idx: their index mode, filling the destination table
+int launch_pack(const MlpPlan& p, const float* params, void* packed, PackIdx t, bool idx, hipStream_t s);
+int launch_adam_multi(const AdamMultiArgs& a, int grid, int nspan, hipStream_t s);
+
+}  // namespace nr
+#pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // Device helpers of the optimizer tail shared by optim.hip (clip, Adam) and the fused
-// step in mlp.hip (Adam that also refreshes the packed MFMA images).
+// step in mlp_pack.hip (Adam that also refreshes the packed MFMA images).
 #pragma once
 
 #include "common.hpp"

@@ -5,8 +5,9 @@ counted `s_waitcnt lgkmcnt` (a compiler-visible LDS load would make hipcc drain 
 in-flight LDS-DMA first).  The compiler then treats those registers as written at once,
 so any instruction it places between such a read and its covering wait that touches
 the register works on the old contents -- the fused backward had exactly that (a copy
-on a branch edge).  tools/lds_hazard.py scans the gfx950 assembly of csrc/mlp.hip
-(default model instances, -DNR_MLP_DEV) for it; every kernel must be clean."""
+on a branch edge).  tools/lds_hazard.py scans the gfx950 assembly of every fused-MLP
+translation unit (csrc/mlp*.hip; default model instances, -DNR_MLP_DEV) for it; every
+kernel must be clean."""
 
 import importlib.util
 import shutil
@@ -36,20 +37,28 @@ def test_checker_flags_a_copy_before_the_wait():
     assert chk.scan(list(enumerate(ok, 1)), "synthetic") == 0
 
 
+# the fused-MLP translation units that hold kernels (mlp.hip: entry points only)
+KERNEL_UNITS = ("mlp_16.hip", "mlp_dw.hip", "mlp_fp32.hip", "mlp_pack.hip")
+
+
 @pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not available")
 def test_mlp_kernels_have_no_asm_lds_read_hazards(tmp_path):
-    src = ROOT / "robust-nerf_amd" / "csrc" / "mlp.hip"
-    out = tmp_path / "mlp_dev.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
-                    "-DNR_MLP_DEV", f"-I{ROOT / 'include'}", f"-I{src.parent}", "--cuda-device-only", "-S", str(src),
-                    "-o", str(out)], check=True, capture_output=True, timeout=600)
-    chk = _checker()
-    text = out.read_text().split("\n")
     import re
-    starts = [i for i, x in enumerate(text) if re.match(r"^_Z\w+:", x)]
-    assert starts, "no kernels in the assembly"
+    csrc = ROOT / "robust-nerf_amd" / "csrc"
+    units = sorted(csrc.glob("mlp*.hip"))
+    assert set(KERNEL_UNITS) <= {u.name for u in units}
+    chk = _checker()
     total = 0
-    for si, s in enumerate(starts):
-        e = starts[si + 1] if si + 1 < len(starts) else len(text)
-        total += chk.scan([(i + 1, text[i]) for i in range(s, e)], text[s].split(":")[0][:60])
-    assert total == 0, f"{total} asm-read register hazard(s) in csrc/mlp.hip (see tools/lds_hazard.py)"
+    for src in units:
+        out = tmp_path / (src.stem + "_dev.s")
+        subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics",
+                        "-ffp-contract=off", "-DNR_MLP_DEV", f"-I{ROOT / 'include'}", f"-I{csrc}", "--cuda-device-only",
+                        "-S", str(src), "-o", str(out)], check=True, capture_output=True, timeout=600)
+        text = out.read_text().split("\n")
+        starts = [i for i, x in enumerate(text) if re.match(r"^_Z\w+:", x)]
+        if src.name in KERNEL_UNITS:
+            assert starts, f"no kernels in the assembly of csrc/{src.name}"
+        for si, s in enumerate(starts):
+            e = starts[si + 1] if si + 1 < len(starts) else len(text)
+            total += chk.scan([(i + 1, text[i]) for i in range(s, e)], text[s].split(":")[0][:60])
+    assert total == 0, f"{total} asm-read register hazard(s) in csrc/mlp*.hip (see tools/lds_hazard.py)"

@@ -10,10 +10,10 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def _pair(precision, seed=0, skips=(4,), use_view_dirs=True):
+def _pair(precision, seed=0, skips=(4,), use_view_dirs=True, **model_kw):
     from noisy_src.config import ModelConfig
     from noisy_src.model import NeRF
-    cfg = ModelConfig(precision=precision, skips=skips, use_view_dirs=use_view_dirs)
+    cfg = ModelConfig(precision=precision, skips=skips, use_view_dirs=use_view_dirs, **model_kw)
     torch.manual_seed(seed)
     oracle = ref.NeRF(cfg)
     torch.manual_seed(seed)
@@ -69,7 +69,11 @@ def _kink_free(oracle, x, d, eps=2e-6):
     return torch.stack(mins, -1).min(-1).values >= eps
 
 
-def _grads(oracle, net, x, d, seed=3, dtype=torch.float32):
+def _grads(oracle, net, x, d, seed=3, dtype=torch.float32, want_in=True):
+    """One backward of the oracle (in `dtype`) and of the HIP net from the same upstream
+    gradients, zero on samples near a ReLU kink.  d is None for a model without view
+    directions; want_in=False leaves the net's inputs without requires_grad (the backward
+    kernel variant that computes no g_x / g_d)."""
     g = torch.Generator().manual_seed(seed)
     M = x.shape[0]
     keep = _kink_free(oracle, x, d).float()[:, None]
@@ -79,10 +83,12 @@ def _grads(oracle, net, x, d, seed=3, dtype=torch.float32):
     if dtype == torch.float64:
         o = ref.NeRF(oracle.config).double()
         o.load_state_dict({k: v.double() for k, v in oracle.state_dict().items()})
-    xr, dr = x.clone().to(dtype).requires_grad_(True), d.clone().to(dtype).requires_grad_(True)
+    xr = x.clone().to(dtype).requires_grad_(True)
+    dr = None if d is None else d.clone().to(dtype).requires_grad_(True)
     wr, ws = o(xr, dr)
     ((wr * gr.to(dtype)).sum() + (ws * gs.to(dtype)).sum()).backward()
-    xg, dg = x.clone().to(DEV).requires_grad_(True), d.clone().to(DEV).requires_grad_(True)
+    xg = x.clone().to(DEV).requires_grad_(want_in)
+    dg = None if d is None else d.clone().to(DEV).requires_grad_(want_in)
     rgb, sig = net(xg, dg)
     ((rgb * gr.to(DEV)).sum() + (sig * gs.to(DEV)).sum()).backward()
     return o, xr, dr, xg, dg, keep
@@ -101,6 +107,43 @@ def test_fp32_backward():
         assert rel < 2e-5, (name, rel)
     for a, b in ((xg.grad, xr.grad), (dg.grad, dr.grad)):
         rel = ((a.double().cpu() - b).norm() / b.norm()).item()
+        assert rel < 2e-5, rel
+
+
+_FP32_BWD_CONFIGS = {
+    "no_view_dirs": dict(use_view_dirs=False),                      # XB=2, DB=0
+    "pos4": dict(pos_freqs=4),                                      # XB=1, DB=1
+    "pos4_no_view_dirs": dict(pos_freqs=4, use_view_dirs=False),    # XB=1, DB=0
+    "depth1": dict(num_hidden_layers=1, skips=()),
+}
+
+
+@pytest.mark.parametrize("want_in", [True, False], ids=["input_grads", "params_only"])
+@pytest.mark.parametrize("name", sorted(_FP32_BWD_CONFIGS))
+def test_fp32_backward_other_instances(name, want_in):
+    """The fp32 backward instances test_fp32_backward does not reach (a position encoding of
+    one block, no view directions, a one-layer trunk; with and without input gradients),
+    under the same bound: parameter gradients, and dL/dx, dL/dd where requested, vs the
+    fp64 oracle on kink-free samples.  M = 300: nine full tiles and a partial one."""
+    oracle, net = _pair("fp32", **_FP32_BWD_CONFIGS[name])
+    x, d = _inputs(300)
+    if not oracle.config.use_view_dirs:
+        d = None
+    o64, xr, dr, xg, dg, keep = _grads(oracle, net, x, d, dtype=torch.float64, want_in=want_in)
+    assert keep.mean() > 0.5
+    for (pname, pr), pg in zip(o64.named_parameters(), net.parameters()):
+        a, b = pg.grad.double().cpu(), pr.grad
+        rel = ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+        print(name, want_in, pname, f"{rel:.3e}")
+        assert rel < 2e-5, (pname, rel)
+    if not want_in:
+        assert xg.grad is None and (dg is None or dg.grad is None)
+        return
+    for a, b in ((xg, xr), (dg, dr)):
+        if a is None:
+            continue
+        rel = ((a.grad.double().cpu() - b.grad).norm() / b.grad.norm()).item()
+        print(name, "input", f"{rel:.3e}")
         assert rel < 2e-5, rel
 
 

@@ -1,5 +1,5 @@
 """GPU: the backward skips 32-sample tiles whose incoming gradient is exactly zero
-(csrc/mlp.hip tile_flags_kernel / select_tile).
+(csrc/mlp_dw.hip tile_flags_kernel / csrc/mlp_dev.hpp select_tile).
 
 A sample with sigma == 0 (alpha = w = 0 and ReLU'(0) = 0, reference rendering.py:83) or
 with its transmittance underflowed to 0 (cumprod of 1 - alpha + 1e-10, rendering.py:87-96)

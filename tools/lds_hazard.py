@@ -7,7 +7,7 @@ covers it and that reads or writes those registers (a copy on a branch edge, say
 works on the old contents.  This scans each kernel in layout order and reports such
 uses; waits retire reads in issue order (lgkmcnt(N) keeps the N youngest pending).
 
-usage: python tools/lds_hazard.py /tmp/mlp_dev.s [kernel-substring]
+usage: python tools/lds_hazard.py /tmp/mlp_16_dev.s [kernel-substring]   (tools/kdev.sh writes /tmp/<unit>_dev.s)
 """
 
 import re

@@ -60,6 +60,8 @@ def short(name: str) -> str:
 
 
 def precision_of(name: str) -> str:
+    if short(name) in ("mlp_fwd_kernel", "mlp_bwd_kernel"):  # the chunk-major kernels: fp32 only
+        return "fp32"
     m = re.search(r"nr::mlp_\w+_kernel<(\d)", name)
     return {"1": "bf16", "0": "fp32", "2": "fp16"}.get(m.group(1), "") if m else ""
 
