@@ -360,6 +360,46 @@ int nr_composite_mse(const float* rgb, const float* sigma, const float* z,
                      float* g_sigma, float* g_rays_d, uint32_t* ticket,
                      void* workspace, nr_stream_t stream);
 
+/* ---- evaluation image tail  (noisy_src/metrics.py:43-116, inference.py:108-125)
+ * Additive to ABI 5.
+ *
+ * nr_image_metrics: compute_ssim (metrics.py:48-116) and compute_mse (metrics.py:43-45)
+ * of one image pair in one pass.  pred / target (H,W,C) fp32 row-major, C = 1 or 3.
+ * g: the 11 one-dimensional Gaussian weights, a HOST array read during the call and
+ * passed to the kernel by value (exp(-(i-5)^2 / (2 1.5^2)) normalised, in fp32, as
+ * metrics._gaussian_window builds them).  The blur is zero-padded (pad 5, no
+ * renormalisation at the borders), per channel, of p, t, p^2, t^2 and p t;
+ * ssim_map = ((2 mu_p mu_t + C1)(2 s_pt + C2)) / ((mu_p^2 + mu_t^2 + C1)(s_p + s_t + C2)).
+ * The fp32 inputs are promoted to double and ALL arithmetic after that is fp64 (a
+ * separable 11-tap blur across, then down).  out (device, 2 doubles, OVERWRITTEN) =
+ * {sum ssim_map, sum (p - t)^2}; the caller divides by H*W*C.  One workgroup per
+ * 32 x 16 tile and channel writes its partials to its own slot of workspace
+ * (nr_image_metrics_workspace_bytes, no zero-initialisation needed) and a second,
+ * one-workgroup launch sums the slots in a fixed order: no atomics, bit-identical
+ * from run to run.  NR_EARG (workspace_bytes: -1) for C not in {1, 3}, H < 1, W < 1,
+ * or more tiles x channels than the workspace indexes with an int (INT_MAX / 256).  */
+int64_t nr_image_metrics_workspace_bytes(int H, int W, int C);
+int nr_image_metrics(const float* pred, const float* target, int H, int W, int C,
+                     const float* g, double C1, double C2, double* out,
+                     void* workspace, nr_stream_t stream);
+/* save_image's quantisation (inference.py:108-111) on the device: src (H,W,C) fp32 ->
+ * bytes (uint8)(clip(x * 255.0f, 0, 255)), truncated, written to row y, columns
+ * [dst_x0, dst_x0 + W) of a frame whose rows are dst_stride bytes apart:
+ * dst[y * dst_stride + (dst_x0 + x) * C + c].  Two calls fill the halves of a
+ * side-by-side comparison frame without a concatenation.  Non-finite input is outside
+ * the contract: 0 is written for it.                                               */
+int nr_frame_u8(const float* src, int H, int W, int C, uint8_t* dst,
+                int64_t dst_stride, int dst_x0, nr_stream_t stream);
+/* depth_to_colormap (inference.py:114-125) then the quantisation above: depth (H,W)
+ * fp32 -> dst (H,W,3) uint8 dense.  n = (d - min) / (max - min + 1e-8f), r = clamp(4n -
+ * 1.5), g = clamp(2 - 4|n - 0.5|), b = clamp(1.5 - 4n): the host function's fp32
+ * operations in its order (no contraction, correctly rounded division), so the bytes
+ * equal the host path's.  Min and max come from per-workgroup partials in workspace
+ * (nr_depth_frame_u8_workspace_bytes), reduced in a fixed order, no atomics.        */
+int64_t nr_depth_frame_u8_workspace_bytes(void);
+int nr_depth_frame_u8(const float* depth, int H, int W, uint8_t* dst,
+                      void* workspace, nr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,14 @@ returns the same summary, and rank 0 writes the JSON files.  Camera noise is dra
 for every view up front, in view order, from the same seed on every rank (the
 reference draws it inside its loop, in the same order; rendering itself draws
 nothing), so the noisy poses match the reference's sequential run.
+
+``render_video`` (inference.py:365-443) shards its frames the same way, and ``main``
+is the reference's command line (inference.py:446-612: ``python -m noisy_src.inference
+ckpt.pt --mode test --rotation_noise 1.0``) with a working ``--mode single``,
+``--precision`` and, under ``torch.distributed.run``, the sharding above.  On a GPU the
+entry point runs the fused image tail (``fused_tail=True``): ``metrics.image_metrics``
+(fp64 SSIM, one read-back per image) and the 8-bit frames of ``frame_u8`` /
+``depth_frame_u8`` written on the device (csrc/image.hip).
 """
 
 from __future__ import annotations
@@ -19,27 +27,28 @@ import json
 import time
 from datetime import datetime
 from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
 from .config import ModelConfig, RenderConfig
-from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim
+from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim, image_metrics
 from .model import NeRF
 from .noise import NoiseConfig, add_noise_to_pose, compute_pose_error, set_noise_seed
 from .rendering import NeRFRenderer
 from .train import render_image
 
 
-def load_checkpoint(checkpoint_path: Path, device: str = "cuda") -> tuple:
+def load_checkpoint(checkpoint_path: Path, device: str = "cuda", precision: Optional[str] = None) -> tuple:
     """Reference inference.py:33-72 -> (renderer, config dict, iteration).  Loads with
-    ``weights_only=True``: a checkpoint is tensors, dicts, lists and scalars only."""
+    ``weights_only=True``: a checkpoint is tensors, dicts, lists and scalars only.
+    ``precision`` overrides the MLP operand precision stored with the checkpoint."""
     ckpt = torch.load(checkpoint_path, map_location=device, weights_only=True)
     cfg = ckpt.get("config", {})
     model_cfg = ModelConfig(**cfg.get("model", {}))
     # MI355X-only knob, kept out of config["model"] so reference loaders accept the file
-    model_cfg.precision = ckpt.get("mi355x", {}).get("precision", model_cfg.precision)
+    model_cfg.precision = precision or ckpt.get("mi355x", {}).get("precision", model_cfg.precision)
     render_cfg = RenderConfig(**cfg.get("render", {}))
     coarse = NeRF(model_cfg).to(device)
     coarse.load_state_dict(ckpt["model_coarse"])
@@ -65,6 +74,66 @@ def depth_to_colormap(depth: torch.Tensor) -> torch.Tensor:
     n = (depth - depth.min()) / (depth.max() - depth.min() + 1e-8)
     return torch.stack([torch.clamp(4 * n - 1.5, 0, 1), torch.clamp(2 - 4 * torch.abs(n - 0.5), 0, 1),
                         torch.clamp(1.5 - 4 * n, 0, 1)], dim=-1)
+
+
+def frame_u8(img: torch.Tensor, out: Optional[torch.Tensor] = None, x0: int = 0) -> torch.Tensor:
+    """``save_image``'s quantisation on the device (``nr_frame_u8``): (H,W,C) fp32 -> a device
+    uint8 frame with the same bytes.  With ``out`` (H, W_out, C) uint8 the image lands in
+    columns [x0, x0 + W): two calls fill a side-by-side comparison frame."""
+    from . import _hip
+    src = img.detach().float().contiguous()
+    sp = _hip.ptr(src)
+    if src.dim() != 3:
+        raise ValueError(f"frame_u8: need an (H,W,C) image, got {tuple(src.shape)}")
+    H, W, C = src.shape
+    if out is None:
+        out = torch.empty(H, W, C, device=src.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or out.dim() != 3 or out.shape[0] != H or out.shape[2] != C \
+            or not 0 <= x0 <= out.shape[1] - W:
+        raise ValueError(f"frame_u8: a {(H, W, C)} image at column {x0} does not fit the frame {tuple(out.shape)}")
+    _hip.call("nr_frame_u8", sp, H, W, C, _hip.ptr(out), out.shape[1] * C, x0, _hip.stream_ptr())
+    return out
+
+
+def depth_frame_u8(depth: torch.Tensor) -> torch.Tensor:
+    """``depth_to_colormap`` and ``save_image``'s quantisation on the device
+    (``nr_depth_frame_u8``): (H,W) depth -> (H,W,3) device uint8, the host path's bytes."""
+    from . import _hip
+    d = depth.detach().float().contiguous()
+    dp = _hip.ptr(d)
+    if d.dim() != 2:
+        raise ValueError(f"depth_frame_u8: need an (H,W) depth map, got {tuple(d.shape)}")
+    out = torch.empty(d.shape[0], d.shape[1], 3, device=d.device, dtype=torch.uint8)
+    ws = torch.empty(int(_hip.call("nr_depth_frame_u8_workspace_bytes")), device=d.device, dtype=torch.uint8)
+    _hip.call("nr_depth_frame_u8", dp, d.shape[0], d.shape[1], _hip.ptr(out), _hip.ptr(ws), _hip.stream_ptr())
+    return out
+
+
+def save_frame_u8(frame: torch.Tensor, path: Path) -> None:
+    """A device uint8 frame -> host bytes -> PNG (the image crosses PCIe as bytes)."""
+    from PIL import Image
+    Image.fromarray(frame.cpu().numpy()).save(path)
+
+
+def _save_view(out_dir: Path, i: int, pred: torch.Tensor, target: torch.Tensor, depth: torch.Tensor,
+               fused_tail: bool) -> None:
+    """The four PNGs of one evaluated view (reference inference.py:232-247)."""
+    if not fused_tail:
+        save_image(pred, out_dir / f"pred_{i:03d}.png")
+        save_image(target, out_dir / f"gt_{i:03d}.png")
+        save_image(torch.cat([target, pred], dim=1), out_dir / f"comparison_{i:03d}.png")
+        save_image(depth_to_colormap(depth), out_dir / f"depth_{i:03d}.png")
+        return
+    H, W, C = pred.shape
+    both = torch.empty(H, 2 * W, C, device=pred.device, dtype=torch.uint8)
+    frame_u8(target, out=both, x0=0)
+    frame_u8(pred, out=both, x0=W)
+    from PIL import Image
+    host = both.cpu().numpy()  # one copy; pred and gt are its halves
+    Image.fromarray(np.ascontiguousarray(host[:, W:])).save(out_dir / f"pred_{i:03d}.png")
+    Image.fromarray(np.ascontiguousarray(host[:, :W])).save(out_dir / f"gt_{i:03d}.png")
+    Image.fromarray(host).save(out_dir / f"comparison_{i:03d}.png")
+    save_frame_u8(depth_frame_u8(depth), out_dir / f"depth_{i:03d}.png")
 
 
 def generate_output_folder_name(mode: str, noise_config: NoiseConfig, scene: str) -> str:
@@ -104,38 +173,57 @@ def _noisy_poses(test_data, noise_config: NoiseConfig):
     return out
 
 
+def _rank0_draws(views, noise_config: NoiseConfig, process_group):
+    """Unseeded noise under a process group: every rank must still render rank 0's draws."""
+    if process_group is None or not noise_config.has_noise or noise_config.seed is not None:
+        return views
+    import torch.distributed as dist
+    if dist.get_world_size(process_group) == 1 or not views:
+        return views
+    device = views[0][0].device
+    obj = [[(p.cpu(), info) for p, info in views]]
+    dist.broadcast_object_list(obj, src=dist.get_global_rank(process_group, 0), group=process_group)
+    return [(p.to(device), info) for p, info in obj[0]]
+
+
 @torch.no_grad()
 def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise_config: NoiseConfig,
                       device: str = "cuda", chunk_size: int = 1024 * 4, process_group=None,
-                      save_images: bool = True, log=print) -> Dict[str, object]:
+                      save_images: bool = True, log=print, fused_tail: bool = False, *,
+                      view_indices: Optional[Sequence[int]] = None, mode: str = "test") -> Dict[str, object]:
     """Reference inference.py:145-318 (same per-image records, summary keys and files),
-    sharded over ``process_group``'s ranks when one is given."""
+    sharded over ``process_group``'s ranks when one is given.  ``fused_tail``: the metrics
+    of a view come from ``metrics.image_metrics`` (fp64 SSIM, one read-back) and its PNGs
+    from the frame kernels (device only, no CPU fallback).  ``view_indices`` restricts the
+    evaluation to those test views (the noise of every view is still drawn, so a view sees
+    the pose it sees in the full run); ``mode`` is recorded in ``experiment_config.json``."""
     rank, world = 0, 1
     if process_group is not None:
         import torch.distributed as dist
         rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
-    views = _noisy_poses(test_data, noise_config)
-    if world > 1 and noise_config.has_noise and noise_config.seed is None:
-        # unseeded noise: every rank must still render rank 0's draws
-        obj = [[(p.cpu(), info) for p, info in views]]
-        dist.broadcast_object_list(obj, src=dist.get_global_rank(process_group, 0), group=process_group)
-        views = [(p.to(test_data.poses.device), info) for p, info in obj[0]]
+    views = _rank0_draws(_noisy_poses(test_data, noise_config), noise_config, process_group)
     lpips_metric = LPIPSMetric(device=device)
-    n_images = test_data.images.shape[0]
+    order = list(range(test_data.images.shape[0])) if view_indices is None else [int(i) for i in view_indices]
+    n_images = len(order)
     if rank == 0:
         log(f"Evaluating {n_images} test images on {world} rank(s)...")
     mine = []
-    for i in range(rank, n_images, world):
+    for i in order[rank::world]:
         pose, noise_info = views[i]
         target = test_data.images[i]
         start = time.time()
         out = render_image(renderer, pose, test_data.H, test_data.W, test_data.focal, chunk_size=chunk_size)
         pred = out["rgb"]
         torch.cuda.synchronize() if pred.is_cuda else None
-        rec = {"image": i, "psnr": compute_psnr(pred, target).item(), "ssim": compute_ssim(pred, target).item(),
-               "mse": compute_mse(pred, target).item(), "render_time": time.time() - start}
+        if fused_tail:
+            m = image_metrics(pred, target)
+            rec = {"image": i, "psnr": m["psnr"], "ssim": m["ssim"], "mse": m["mse"],
+                   "render_time": time.time() - start}
+        else:
+            rec = {"image": i, "psnr": compute_psnr(pred, target).item(), "ssim": compute_ssim(pred, target).item(),
+                   "mse": compute_mse(pred, target).item(), "render_time": time.time() - start}
         if noise_info:
             rec.update({f"noise_{k}": v for k, v in noise_info.items()})
         lp = lpips_metric(pred, target) if lpips_metric.available else None
@@ -143,10 +231,7 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
             rec["lpips"] = lp.item()
         mine.append(rec)
         if save_images:
-            save_image(pred, output_dir / f"pred_{i:03d}.png")
-            save_image(target, output_dir / f"gt_{i:03d}.png")
-            save_image(torch.cat([target, pred], dim=1), output_dir / f"comparison_{i:03d}.png")
-            save_image(depth_to_colormap(out["depth"]), output_dir / f"depth_{i:03d}.png")
+            _save_view(output_dir, i, pred, target, out["depth"], fused_tail)
         log(f"  Image {i + 1}/{n_images}: PSNR={rec['psnr']:.2f}, SSIM={rec['ssim']:.4f}, "
             f"time={rec['render_time']:.2f}s")
     if world > 1:
@@ -177,12 +262,199 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
         (output_dir / "per_image_metrics.json").write_text(json.dumps(per_image, indent=2))
         (output_dir / "test_metrics.json").write_text(json.dumps(avg, indent=2))
         (output_dir / "experiment_config.json").write_text(json.dumps({
-            "mode": "test",
+            "mode": mode,
             "noise_config": {"rotation_noise_deg": noise_config.rotation_noise_deg,
                              "translation_noise": noise_config.translation_noise, "seed": noise_config.seed},
             "timestamp": datetime.now().isoformat(), "output_dir": str(output_dir), "ranks": world}, indent=2))
     return avg
 
 
-__all__ = ["load_checkpoint", "render_image", "save_image", "depth_to_colormap", "generate_output_folder_name",
-           "create_spiral_poses", "evaluate_test_set"]
+def _noisy_frame_poses(poses: torch.Tensor, noise_config: NoiseConfig):
+    """Every video frame's noisy pose in frame order, as the reference's loop draws them
+    (inference.py:383-402), in the (pose, info) form of ``_noisy_poses``."""
+    if noise_config.seed is not None:
+        set_noise_seed(noise_config.seed)
+    out = []
+    for i in range(poses.shape[0]):
+        pose = poses[i]
+        if noise_config.has_noise:
+            pose, _ = add_noise_to_pose(pose, rotation_noise_deg=noise_config.rotation_noise_deg,
+                                        translation_noise=noise_config.translation_noise)
+        out.append((pose, {}))
+    return out
+
+
+@torch.no_grad()
+def render_video(renderer: NeRFRenderer, poses: torch.Tensor, H: int, W: int, focal: float, output_dir: Path,
+                 noise_config: NoiseConfig, fps: int = 30, chunk_size: int = 1024 * 4, *, process_group=None,
+                 fused_tail: bool = False, log=print) -> Path:
+    """Reference inference.py:365-443: ``frames/frame_%04d.png``, ``video_config.json`` and,
+    where ``ffmpeg`` runs, ``video.mp4`` (otherwise the frames directory is returned).
+    Every frame's noise is drawn up front in frame order on every rank, so the poses equal
+    the reference's sequential run; with a process group rank r renders frames r, r+N, ...
+    and rank 0 alone writes the JSON and runs ``ffmpeg``.  ``fused_tail``: frames are
+    quantised on the device (``frame_u8``) and cross to the host as bytes."""
+    rank, world = 0, 1
+    if process_group is not None:
+        import torch.distributed as dist
+        rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
+    output_dir = Path(output_dir)
+    frames_dir = output_dir / "frames"
+    frames_dir.mkdir(parents=True, exist_ok=True)
+    frames = _rank0_draws(_noisy_frame_poses(poses, noise_config), noise_config, process_group)
+    n_frames = len(frames)
+    if rank == 0:
+        log(f"Rendering {n_frames} frames on {world} rank(s)...")
+        if noise_config.has_noise:
+            log(f"  With noise: rot={noise_config.rotation_noise_deg}°, trans={noise_config.translation_noise}")
+    for i in range(rank, n_frames, world):
+        rgb = render_image(renderer, frames[i][0], H, W, focal, chunk_size=chunk_size)["rgb"]
+        path = frames_dir / f"frame_{i:04d}.png"
+        if fused_tail:
+            save_frame_u8(frame_u8(rgb), path)
+        else:
+            save_image(rgb, path)
+        if (i + 1) % 10 == 0:
+            log(f"  Rendered {i + 1}/{n_frames} frames")
+    if world > 1:
+        dist.barrier(process_group)
+    result = [frames_dir]
+    if rank == 0:
+        (output_dir / "video_config.json").write_text(json.dumps({
+            "n_frames": n_frames, "fps": fps,
+            "noise_config": {"rotation_noise_deg": noise_config.rotation_noise_deg,
+                             "translation_noise": noise_config.translation_noise, "seed": noise_config.seed},
+            "timestamp": datetime.now().isoformat()}, indent=2))
+        video_path = output_dir / "video.mp4"
+        try:
+            import subprocess
+            subprocess.run(["ffmpeg", "-y", "-framerate", str(fps), "-i", str(frames_dir / "frame_%04d.png"),
+                            "-c:v", "libx264", "-pix_fmt", "yuv420p", str(video_path)], check=True,
+                           capture_output=True)
+            log(f"Video saved to {video_path}")
+            result = [video_path]
+        except Exception as e:  # no ffmpeg, or it failed: the frames are the result (reference :438-441)
+            log(f"Could not create video (ffmpeg required): {e}")
+            log(f"Frames saved to {frames_dir}")
+    if world > 1:
+        dist.broadcast_object_list(result, src=dist.get_global_rank(process_group, 0), group=process_group)
+    return result[0]
+
+
+def build_arg_parser():
+    """Reference inference.py:448-503 flags (same names and defaults) plus ``--precision``
+    and ``--image_index``."""
+    import argparse
+    ap = argparse.ArgumentParser(
+        prog="python -m noisy_src.inference", description="NeRF inference with optional camera noise (MI355X HIP path)",
+        formatter_class=argparse.RawDescriptionHelpFormatter,
+        epilog="Examples:\n"
+               "  python -m noisy_src.inference checkpoint.pt --mode test --rotation_noise 1.0 --noise_seed 42\n"
+               "  python -m noisy_src.inference checkpoint.pt --mode video --rotation_noise 0.5\n"
+               "  python -m noisy_src.inference checkpoint.pt --mode single --image_index 3\n")
+    ap.add_argument("checkpoint", type=Path, help="Path to checkpoint file")
+    ap.add_argument("--mode", type=str, default="test", choices=["test", "video", "single"], help="Inference mode")
+    ap.add_argument("--scene", type=str, default=None, help="Scene name (auto-detected from config if not provided)")
+    ap.add_argument("--data_root", type=Path, default=None, help="Data root directory")
+    ap.add_argument("--output_dir", type=Path, default=None, help="Output directory (auto-generated if not provided)")
+    ap.add_argument("--device", type=str, default="cuda", help="Device")
+    ap.add_argument("--precision", type=str, default=None, choices=["fp32", "bf16", "fp16"],
+                    help="MLP operand precision (default: the checkpoint's own; fp32 = the reference's numerics)")
+    ap.add_argument("--image_index", type=int, default=0, help="Test view rendered by --mode single")
+    noise = ap.add_argument_group("Noise Options")
+    noise.add_argument("--rotation_noise", type=float, default=0.0,
+                       help="Rotation noise std in degrees (default: 0 = no noise)")
+    noise.add_argument("--translation_noise", type=float, default=0.0,
+                       help="Translation noise std in scene units (default: 0 = no noise)")
+    noise.add_argument("--noise_seed", type=int, default=None, help="Random seed for reproducible noise")
+    video = ap.add_argument_group("Video Options")
+    video.add_argument("--n_frames", type=int, default=120, help="Number of frames for video")
+    video.add_argument("--fps", type=int, default=30, help="Video FPS")
+    perf = ap.add_argument_group("Performance Options")
+    perf.add_argument("--chunk_size", type=int, default=1024 * 4, help="Rays per chunk (default: 4096)")
+    return ap
+
+
+def main(argv=None) -> None:
+    """``python -m noisy_src.inference`` (reference inference.py:446-612), or under
+    ``torchrun``: the test views / video frames are sharded over the ranks."""
+    from .data import load_blender_data
+    from .engine import init_distributed
+
+    a = build_arg_parser().parse_args(argv)
+    noise_config = NoiseConfig(rotation_noise_deg=a.rotation_noise, translation_noise=a.translation_noise,
+                               seed=a.noise_seed)
+    pg, rank, world, device = init_distributed(a.device)
+    log = print if rank == 0 else (lambda *_, **__: None)
+    try:
+        log(f"Loading checkpoint: {a.checkpoint}")
+        renderer, config, iteration = load_checkpoint(a.checkpoint, device, precision=a.precision)
+        log(f"Loaded model from iteration {iteration}")
+        scene = a.scene or config.get("data", {}).get("scene_name", "lego")
+        log(f"Scene: {scene}")
+        if a.output_dir is None:
+            name = [generate_output_folder_name(a.mode, noise_config, scene)]
+            if world > 1:  # one shared directory name for all ranks (rank 0's timestamp)
+                import torch.distributed as dist
+                dist.broadcast_object_list(name, src=0, group=pg)
+            output_dir = a.checkpoint.parent / name[0]
+        else:
+            output_dir = a.output_dir
+        log(f"Output directory: {output_dir}")
+        data_root = a.data_root if a.data_root is not None else Path(__file__).resolve().parents[1] / "data" / "raw"
+        img_scale = config.get("data", {}).get("img_scale", 0.5)
+        fused = device.startswith("cuda")
+        bar = "=" * 60
+        if a.mode in ("test", "single"):
+            log("\nLoading test data...")
+            test_data = load_blender_data(data_root, scene, "test", img_scale, device)
+            only = None
+            if a.mode == "single":
+                if not 0 <= a.image_index < test_data.images.shape[0]:
+                    raise SystemExit(f"--image_index {a.image_index} is outside the {test_data.images.shape[0]} "
+                                     "test views")
+                only = [a.image_index]
+            log(f"\n{bar}\n" + ("Test Set Evaluation" if only is None else f"Test view {a.image_index}"))
+            if noise_config.has_noise:
+                log(f"  Rotation noise:    {noise_config.rotation_noise_deg}° (std)")
+                log(f"  Translation noise: {noise_config.translation_noise} (std)")
+                if noise_config.seed is not None:
+                    log(f"  Noise seed:        {noise_config.seed}")
+            else:
+                log("  Mode: Clean (no noise)")
+            log(f"{bar}\n")
+            m = evaluate_test_set(renderer, test_data, output_dir, noise_config, device, a.chunk_size,
+                                  process_group=pg, log=log, fused_tail=fused, view_indices=only, mode=a.mode)
+            log(f"\n{bar}\nTest Set Results:")
+            log(f"  PSNR:  {m['psnr_mean']:.2f} ± {m['psnr_std']:.2f} dB")
+            log(f"  SSIM:  {m['ssim_mean']:.4f} ± {m['ssim_std']:.4f}")
+            if "lpips_mean" in m:
+                log(f"  LPIPS: {m['lpips_mean']:.4f} ± {m['lpips_std']:.4f}")
+            if noise_config.has_noise and "actual_noise" in m:
+                act = m["actual_noise"]
+                log("\nActual Noise Applied:")
+                log(f"  Rotation error:    {act['rotation_error_mean_deg']:.3f} ± {act['rotation_error_std_deg']:.3f}°")
+                log(f"  Translation error: {act['translation_error_mean']:.4f} ± {act['translation_error_std']:.4f}")
+            log(f"{bar}\nResults saved to: {output_dir}")
+        else:
+            log("\nLoading data for camera parameters...")
+            data = load_blender_data(data_root, scene, "train", img_scale, device)
+            log("\nGenerating spiral poses...")
+            poses = create_spiral_poses(n_frames=a.n_frames, device=device)
+            log("\nRendering video...")
+            video_path = render_video(renderer, poses, data.H, data.W, data.focal, output_dir, noise_config, a.fps,
+                                      chunk_size=a.chunk_size, process_group=pg, fused_tail=fused, log=log)
+            log(f"Video saved to: {video_path}")
+        log("\nDone!")
+    finally:
+        if pg is not None:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+
+
+__all__ = ["load_checkpoint", "render_image", "save_image", "depth_to_colormap", "frame_u8", "depth_frame_u8",
+           "save_frame_u8", "generate_output_folder_name", "create_spiral_poses", "evaluate_test_set", "render_video",
+           "main"]
+
+if __name__ == "__main__":
+    main()
