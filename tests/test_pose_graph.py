@@ -141,8 +141,16 @@ def _fresh_pack(net):
     return out
 
 
-def _pose_trainer(precision, rc, batch_size=128, seed=17):
-    """3 views of 16 x 16, the fixture's noisy initial poses as the learnable ones."""
+def _rot0():
+    """Live rotation deltas (theta ~ 0.05 rad) for the 3 views."""
+    return 0.05 * torch.randn(3, 3, generator=torch.Generator().manual_seed(23))
+
+
+def _pose_trainer(precision, rc, batch_size=128, seed=17, start="zero"):
+    """3 views of 16 x 16, the fixture's noisy initial poses as the learnable ones.  ``start``:
+    "zero" deltas (the reference's start: the rotation gradient is exactly 0 for ever),
+    "rot0" (rotation deltas from ``_rot0``) or "fixed_small_angle" (zero deltas, the opt-in
+    exact derivative at w = 0) -- the last two train the rotations."""
     from noisy_src.config import ModelConfig
     from noisy_src.data import synthetic_blender_data
     from noisy_src.data_pose_opt import PixelDataset, PixelSampler
@@ -154,7 +162,10 @@ def _pose_trainer(precision, rc, batch_size=128, seed=17):
     sampler = PixelSampler(PixelDataset(data), batch_size=batch_size)
     torch.manual_seed(seed)
     mc, mf = create_nerf(ModelConfig(precision=precision))
-    cam = CameraPoseParameters(init[:3].to(DEV))
+    cam = CameraPoseParameters(init[:3].to(DEV), fixed_small_angle=start == "fixed_small_angle")
+    if start == "rot0":
+        with torch.no_grad():
+            cam.rotation_deltas.copy_(_rot0().to(DEV))
     return PoseTrainer(mc.to(DEV), mf.to(DEV), cam, sampler, rc)
 
 
@@ -181,15 +192,22 @@ def _run(step, batches):
     return losses
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_graphed_pose_trainer_equals_eager(precision):
+@pytest.mark.parametrize("precision,start", [
+    pytest.param("fp32", "zero", id="fp32"), pytest.param("bf16", "zero", id="bf16"),
+    pytest.param("fp32", "rot0", id="fp32-rot0"), pytest.param("bf16", "rot0", id="bf16-rot0"),
+    pytest.param("fp32", "fixed_small_angle", id="fp32-fixed_small_angle"),
+    pytest.param("bf16", "fixed_small_angle", id="bf16-fixed_small_angle")])
+def test_graphed_pose_trainer_equals_eager(precision, start):
     """Frozen and optimising replays interleaved (F F O O O F O; warmup=1: the first step of
     each shape is eager, the second is captured) equal the eager PoseTrainer: losses,
-    parameters, packed images, poses, LR, Adam counters and moments, bit for bit."""
+    parameters, packed images, poses, LR, Adam counters and moments, bit for bit.  From
+    zero deltas the rotation gradient is exactly 0 on both sides; from ``rot0`` and with
+    ``fixed_small_angle`` it is live, so a replay that failed to zero or re-read a buffer of
+    the rotation-gradient chain would differ, and the rotations must have moved."""
     from noisy_src.config import RenderConfig
     from noisy_src.engine import GraphedPoseTrainer
     rc = RenderConfig(num_samples=32, num_samples_fine=32)
-    eager, tr_g = _pose_trainer(precision, rc), _pose_trainer(precision, rc)
+    eager, tr_g = _pose_trainer(precision, rc, start=start), _pose_trainer(precision, rc, start=start)
     assert torch.equal(eager.model_fine.flat_params(), tr_g.model_fine.flat_params())
     batches = _batches(eager, rc, len(SEQUENCE))
     le = _run(eager.step, batches)
@@ -205,6 +223,11 @@ def test_graphed_pose_trainer_equals_eager(precision):
     assert torch.equal(ca.rotation_deltas.detach(), cb.rotation_deltas.detach())
     assert torch.equal(ca.translation_deltas.detach(), cb.translation_deltas.detach())
     assert cb.translation_deltas.detach().abs().max() > 0
+    rot_start = _rot0().to(DEV) if start == "rot0" else torch.zeros(3, 3, device=DEV)
+    if start == "zero":
+        assert torch.equal(cb.rotation_deltas.detach(), rot_start)  # the reference's quirk
+    else:
+        assert (cb.rotation_deltas.detach() - rot_start).abs().amax(dim=1).min() > 1e-5  # every view's rotation moved
     n_opt = sum(SEQUENCE)
     for oa, ob, steps in ((eager.optimizer_nerf, tr_g.optimizer_nerf, len(SEQUENCE)),
                           (eager.optimizer_poses, tr_g.optimizer_poses, n_opt)):
