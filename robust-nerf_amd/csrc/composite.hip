@@ -84,7 +84,8 @@ __global__ void composite_bwd_kernel(const float* rgb, const float* sigma, const
         T = T * (1.0f - st.alpha + 1e-10f);
     }
     // pass 2: reverse recurrence
-    float R = 0.f, Gn = 0.f, an = 0.f, tn = 0.f, g_norm = 0.f;
+    float R = 0.f, Gn = 0.f, an = 0.f, tn = 0.f;
+    double gn64 = 0.0;  // g_norm, summed in fp64 as in the wave kernels (wave_sum_f64)
     for (int i = S - 1; i >= 0; --i) {
         const SampleTerms st = sample_terms(sigma, z, noise, base, i, S, dnorm);
         const int64_t q = 3 * (base + i);
@@ -102,12 +103,13 @@ __global__ void composite_bwd_kernel(const float* rgb, const float* sigma, const
         const float g_x = -g_alpha * st.e;
         const float delta = st.delta_raw * dnorm;
         g_sigma[base + i] = (st.sig > 0.f) ? -g_x * delta : 0.f;
-        g_norm += g_x * (-st.sig * st.delta_raw);
+        if (g_rd) gn64 += static_cast<double>(g_x * (-st.sig * st.delta_raw));
         Gn = G;
         an = st.alpha;
         tn = 1.0f - st.alpha + 1e-10f;
     }
     if (g_rd) {
+        const float g_norm = static_cast<float>(gn64);
         g_rd[3 * b] += g_norm * dx / dnorm;
         g_rd[3 * b + 1] += g_norm * dy / dnorm;
         g_rd[3 * b + 2] += g_norm * dz / dnorm;
@@ -127,6 +129,18 @@ __global__ void composite_bwd_kernel(const float* rgb, const float* sigma, const
 constexpr int kCompK = 8;
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// dL/d|d| = sum_i g_x_i (-sigma_i delta_i) is a sum of S signed fp32 products that
+// largely cancel, and one number per ray carries the whole g_rays_d: summed in fp32 its
+// error was set by the accumulation, not by the terms (6.9 half-ulps of the result at
+// S = 512 against 0.4 for the same terms summed in fp64, tests/test_edge_shapes.py).  The
+// products stay fp32; only their sum runs in fp64, one add per sample and six shuffles
+// per ray, in every backward kernel alike, and only when g_rays_d is wanted.
+__device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
     return v;
@@ -278,7 +292,7 @@ __global__ __launch_bounds__(256) void composite_bwd_wave_kernel(
     }
     float X = __shfl_down(qa, 1);
     if (lane == 63) X = 0.f;
-    float g_norm = 0.f;
+    double gn64 = 0.0;  // g_norm: see wave_sum_f64
 #pragma unroll
     for (int k = 0; k < kCompK; ++k) {
         const int i = i0 + k;
@@ -293,10 +307,10 @@ __global__ __launch_bounds__(256) void composite_bwd_wave_kernel(
             const float g_alpha = Ti * (GG[k] - R);
             const float g_x = -g_alpha * ee[k];
             g_sigma[base + i] = (sg[k] > 0.f) ? -g_x * (dr[k] * dnorm) : 0.f;
-            g_norm += g_x * (-sg[k] * dr[k]);
+            if (g_rd) gn64 += static_cast<double>(g_x * (-sg[k] * dr[k]));  // launch-uniform
         }
     }
-    g_norm = wave_sum(g_norm);
+    const float g_norm = g_rd ? static_cast<float>(wave_sum_f64(gn64)) : 0.f;
     if (g_rd && lane == 0) {
         g_rd[3 * b] += g_norm * dx / dnorm;
         g_rd[3 * b + 1] += g_norm * dy / dnorm;
@@ -423,7 +437,7 @@ __device__ __forceinline__ void composite_mse_ray(const float* rgb, const float*
     }
     float X = __shfl_down(qa, 1);
     if (lane == 63) X = 0.f;
-    float g_norm = 0.f;
+    double gn64 = 0.0;  // g_norm: see wave_sum_f64
 #pragma unroll
     for (int k = 0; k < kCompK; ++k) {
         const int i = i0 + k;
@@ -438,10 +452,10 @@ __device__ __forceinline__ void composite_mse_ray(const float* rgb, const float*
             const float g_alpha = Ti * (GG[k] - R);
             const float g_x = -g_alpha * ee[k];
             g_sigma[base + i] = (sg[k] > 0.f) ? -g_x * (dr[k] * dnorm) : 0.f;
-            g_norm += g_x * (-sg[k] * dr[k]);
+            if (g_rd) gn64 += static_cast<double>(g_x * (-sg[k] * dr[k]));  // launch-uniform
         }
     }
-    g_norm = wave_sum(g_norm);
+    const float g_norm = g_rd ? static_cast<float>(wave_sum_f64(gn64)) : 0.f;
     if (g_rd && lane == 0) {
         g_rd[3 * b] += g_norm * dx / dnorm;
         g_rd[3 * b + 1] += g_norm * dy / dnorm;
