@@ -155,6 +155,19 @@ int nr_positional_encoding_bwd(const float* x, int64_t M, int C, int num_freqs,
                                int include_input, int log_sampling,
                                const float* g_out, float* g_x,
                                nr_stream_t stream);
+/* The windowed encoding (no reference counterpart; additive to ABI 5): frequency
+ * k's sin and cos columns times w[k]; the raw input columns are not weighted.
+ * w: num_freqs floats in DEVICE memory, read by the kernel (capturable; a replay
+ * sees the values of its time), nullable = all ones.                          */
+int nr_positional_encoding_windowed(const float* x, int64_t M, int C,
+                                    int num_freqs, int include_input,
+                                    int log_sampling, const float* w,
+                                    float* out, nr_stream_t stream);
+int nr_positional_encoding_windowed_bwd(const float* x, int64_t M, int C,
+                                        int num_freqs, int include_input,
+                                        int log_sampling, const float* w,
+                                        const float* g_out, float* g_x,
+                                        nr_stream_t stream);
 
 /* ---- A9: sample_pdf  (noisy_src/rays.py:213-279) -------------------------
  * bins (B,Nb), weights (B,Nb-1), u (B,Ns) nullable -> det=True linspace(0,1).
@@ -223,6 +236,31 @@ int64_t nr_mlp_workspace_bytes(const NrMlpConfig* cfg, int64_t M);
  * forward (W) and backward (W^T) kernels.  Call after every optimizer step. */
 int nr_mlp_pack(const NrMlpConfig* cfg, const float* params, void* packed,
                 nr_stream_t stream);
+
+/* Coarse-to-fine positional encoding (no reference counterpart; additive to ABI 5).
+ * A window puts a weight on every frequency of the two encoders the MLP fuses:
+ * gamma_w(x) = [x | w_0 sin x, w_0 cos x | ... | w_{L-1} sin 2^{L-1} x, w_{L-1} cos ..].
+ * w_pos (pos_freqs floats) and w_dir (dir_freqs floats; NULL without
+ * use_view_dirs) are DEVICE pointers read inside the kernels, each nullable =
+ * all ones.  No allocation, no synchronisation: both calls are capturable.
+ *
+ * nr_mlp_fold_window: W . (s * gamma) = (W * s) . gamma, so the window is folded
+ * into the images: every element of the W and W^T images that holds an encoding
+ * column of layer 0, of the layer after each skip, or of dir_linear is rewritten
+ * as convert(params[row, col] * s(col)), s = 1 on the 3 raw columns and
+ * w[(c - 3) / 6] on encoding column c, by the index maps and conversions of
+ * nr_mlp_pack.  The forward and the input gradients then are the windowed
+ * network's.  With all-ones weights packed is left byte-identical to nr_mlp_pack's.
+ * nr_mlp_pack and a nr_adam_multi refresh write those elements unfolded again.
+ *
+ * nr_mlp_window_grad: the backward on folded images leaves dL/d(W * s) in
+ * g_params; this multiplies the same columns by s(col) in place, giving dL/dW
+ * (exactly zero where w_k = 0).                                              */
+int nr_mlp_fold_window(const NrMlpConfig* cfg, const float* params,
+                       const float* w_pos, const float* w_dir, void* packed,
+                       nr_stream_t stream);
+int nr_mlp_window_grad(const NrMlpConfig* cfg, const float* w_pos,
+                       const float* w_dir, float* g_params, nr_stream_t stream);
 
 /* Forward: x (M,3) positions, d (M,3) view directions -> rgb (M,3) in [0,1],
  * sigma (M) >= 0.  saved (nr_mlp_saved_bytes) nullable: inference only.   */

@@ -4,7 +4,7 @@
 //   mlp_fp32.hip  fp32 parity mode: chunk-major forward and backward dX chain
 //   mlp_16.hip    bf16 / fp16: row-block-major forward, dX chain, input gradients
 //   mlp_dw.hip    active-tile flags, the dW GEMM and its deterministic split-M reduction
-//   mlp_pack.hip  weight packing and the fused optimizer step
+//   mlp_pack.hip  weight packing, the fused optimizer step, the positional-encoding window
 //   mlp_dev.hpp   the device helpers they share
 //
 // Reference: noisy_src/model.py:20-221 — PositionalEncoding (no pi), 8x256 ReLU
@@ -84,6 +84,26 @@ int nr_mlp_pack(const NrMlpConfig* cfg, const float* params, void* packed, nr_st
     NR_REQUIRE(params && packed, "nr_mlp_pack: null pointer");
     NR_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "nr_mlp_pack: packed must be 16-byte aligned");
     return launch_pack(p, params, packed, PackIdx{nullptr, 0}, false, static_cast<hipStream_t>(stream));
+}
+
+int nr_mlp_fold_window(const NrMlpConfig* cfg, const float* params, const float* w_pos, const float* w_dir,
+                       void* packed, nr_stream_t stream) {
+    MlpPlan p;
+    if (!plan_or_error(cfg, &p)) return NR_EARG;
+    NR_REQUIRE(params && packed, "nr_mlp_fold_window: null pointer");
+    NR_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "nr_mlp_fold_window: packed must be 16-byte aligned");
+    NR_REQUIRE(!w_dir || p.use_vd, "nr_mlp_fold_window: w_dir without use_view_dirs");
+    return launch_fold_window(p, params, packed, w_pos, w_dir, static_cast<hipStream_t>(stream));
+}
+
+int nr_mlp_window_grad(const NrMlpConfig* cfg, const float* w_pos, const float* w_dir, float* g_params,
+                       nr_stream_t stream) {
+    MlpPlan p;
+    if (!plan_or_error(cfg, &p)) return NR_EARG;
+    NR_REQUIRE(g_params, "nr_mlp_window_grad: null pointer");
+    NR_REQUIRE(!w_dir || p.use_vd, "nr_mlp_window_grad: w_dir without use_view_dirs");
+    if (!w_pos && !w_dir) return NR_OK;  // all ones
+    return launch_window_grad(p, w_pos, w_dir, g_params, static_cast<hipStream_t>(stream));
 }
 
 int64_t nr_mlp_pack_table_bytes(const NrMlpConfig* cfg) {

@@ -214,6 +214,12 @@ struct AdamMultiArgs {
 // nr_mlp_pack's four kernels; idx: their index mode, filling the destination table
 int launch_pack(const MlpPlan& p, const float* params, void* packed, PackIdx t, bool idx, hipStream_t s);
 int launch_adam_multi(const AdamMultiArgs& a, int grid, int nspan, hipStream_t s);
+// positional-encoding window (w_pos: L floats, w_dir: Ld floats, device, nullable = ones):
+// the images' encoding columns rewritten from params times the window, and the flat
+// gradient's encoding columns times it
+int launch_fold_window(const MlpPlan& p, const float* params, void* packed, const float* w_pos, const float* w_dir,
+                       hipStream_t s);
+int launch_window_grad(const MlpPlan& p, const float* w_pos, const float* w_dir, float* g_params, hipStream_t s);
 
 }  // namespace nr
 #pragma GCC visibility pop

@@ -1,5 +1,6 @@
 // Weight packing of the fused NeRF MLP (the MFMA fragment images of mlp_plan.hpp, all
-// precisions) and the fused optimizer step that refreshes them in place.
+// precisions), the fused optimizer step that refreshes them in place, and the
+// positional-encoding window folded into their encoding columns.
 #include <cstring>
 
 #include "mlp_dev.hpp"
@@ -50,6 +51,51 @@ __device__ __forceinline__ int pack_col(const PackArgs& a, int l, int kb, int c)
     return -1;
 }
 
+// Image element e of layer l's W (bwd: W^T) image in pack order: the W entry it holds
+// (col < 0: padding) and the element of the image it is stored at.
+struct PackLoc {
+    int row, col;
+    int64_t dst_e;
+};
+__device__ __forceinline__ PackLoc pack_locate(const PackArgs& a, int l, int64_t e, bool bwd) {
+    const bool bf = a.prec != NR_PREC_FP32;  // 16-bit image (bf16 or fp16)
+    const int epl = bf ? 8 : 4, fpb = bf ? 2 : 4;
+    const int64_t frag = e / (64 * epl);
+    const int lane = static_cast<int>((e / epl) % 64);
+    const int el = static_cast<int>(e % epl);
+    const int64_t blk = frag / fpb;
+    const int sub = static_cast<int>(frag % fpb);
+    const int h = lane >> 5, i = lane & 31;
+    const int kk = bf ? 16 * sub + 8 * (el >> 2) + 4 * h + (el & 3) : acc_row(4 * sub + el, h);
+    PackLoc o;
+    o.dst_e = e;
+    if (!bwd) {  // W: A[i][k] = W[32nb + i][col(kb, k)]
+        // fp32: chunk kb, row block nb (chunk-major); 16-bit: row block nb, k block kb,
+        // then the row block's bias fragment (row-block major, mlp_fwd_rbm.inc)
+        const int kb = static_cast<int>(bf ? blk % a.KB[l] : blk / a.NB[l]);
+        const int nb = static_cast<int>(bf ? blk / a.KB[l] : blk % a.NB[l]);
+        o.row = 32 * nb + i;
+        o.col = pack_col(a, l, kb, kk);
+        if (bf) o.dst_e = ((static_cast<int64_t>(nb) * (2 * a.KB[l] + 1) + 2 * kb + sub) * 64 + lane) * epl + el;
+    } else {  // W^T: A[i][k] = W[32ob + k][col(ib, i)], chunk ob, row block ib
+        const int ob = static_cast<int>(blk / a.KB[l]);
+        const int ib = static_cast<int>((blk % a.KB[l] + a.bwd_rot[l]) % a.KB[l]);
+        o.row = 32 * ob + kk;
+        o.col = pack_col(a, l, ib, i);
+    }
+    return o;
+}
+
+// v, converted to the image's precision, into element dst_e of layer l's W (bwd: W^T) image
+__device__ __forceinline__ void pack_store(const PackArgs& a, int l, bool bwd, int64_t dst_e, float v) {
+    char* dst = a.packed + (bwd ? a.pkb[l] : a.pk[l]);
+    if (a.prec != NR_PREC_FP32)
+        reinterpret_cast<unsigned short*>(dst)[dst_e] =
+            a.prec == NR_PREC_FP16 ? __builtin_bit_cast(unsigned short, static_cast<_Float16>(v)) : bf16_bits(v);
+    else
+        reinterpret_cast<float*>(dst)[dst_e] = v;
+}
+
 template <bool IDX>
 __global__ void mlp_pack_kernel(PackArgs a, PackIdx t) {
     const int64_t g = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -60,44 +106,77 @@ __global__ void mlp_pack_kernel(PackArgs a, PackIdx t) {
     int64_t e = g - a.cum[l];
     const bool bwd = e >= img;
     if (bwd) e -= img;
-    const bool bf = a.prec != NR_PREC_FP32;  // 16-bit image (bf16 or fp16)
-    const int epl = bf ? 8 : 4, fpb = bf ? 2 : 4;
-    const int64_t frag = e / (64 * epl);
-    const int lane = static_cast<int>((e / epl) % 64);
-    const int el = static_cast<int>(e % epl);
-    const int64_t blk = frag / fpb;
-    const int sub = static_cast<int>(frag % fpb);
-    const int h = lane >> 5, i = lane & 31;
-    const int kk = bf ? 16 * sub + 8 * (el >> 2) + 4 * h + (el & 3) : acc_row(4 * sub + el, h);
-    int row, col;
-    int64_t dst_e = e;
-    if (!bwd) {  // W: A[i][k] = W[32nb + i][col(kb, k)]
-        // fp32: chunk kb, row block nb (chunk-major); 16-bit: row block nb, k block kb,
-        // then the row block's bias fragment (row-block major, mlp_fwd_rbm.inc)
-        const int kb = static_cast<int>(bf ? blk % a.KB[l] : blk / a.NB[l]);
-        const int nb = static_cast<int>(bf ? blk / a.KB[l] : blk % a.NB[l]);
-        row = 32 * nb + i;
-        col = pack_col(a, l, kb, kk);
-        if (bf) dst_e = ((static_cast<int64_t>(nb) * (2 * a.KB[l] + 1) + 2 * kb + sub) * 64 + lane) * epl + el;
-    } else {  // W^T: A[i][k] = W[32ob + k][col(ib, i)], chunk ob, row block ib
-        const int ob = static_cast<int>(blk / a.KB[l]);
-        const int ib = static_cast<int>((blk % a.KB[l] + a.bwd_rot[l]) % a.KB[l]);
-        row = 32 * ob + kk;
-        col = pack_col(a, l, ib, i);
-    }
+    const bool bf = a.prec != NR_PREC_FP32;
+    const PackLoc o = pack_locate(a, l, e, bwd);
     if constexpr (IDX) {
-        if (col >= 0)
-            put_dst(t, bwd ? 1 : 0, a.w_off[l] + static_cast<int64_t>(row) * a.in[l] + col,
-                    (bwd ? a.pkb[l] : a.pk[l]) + dst_e * (bf ? 2 : 4), bf ? dst16(a.prec) : kDstF32);
+        if (o.col >= 0)
+            put_dst(t, bwd ? 1 : 0, a.w_off[l] + static_cast<int64_t>(o.row) * a.in[l] + o.col,
+                    (bwd ? a.pkb[l] : a.pk[l]) + o.dst_e * (bf ? 2 : 4), bf ? dst16(a.prec) : kDstF32);
         return;
     }
-    const float v = col >= 0 ? a.params[a.w_off[l] + static_cast<int64_t>(row) * a.in[l] + col] : 0.f;
-    char* dst = a.packed + (bwd ? a.pkb[l] : a.pk[l]);
-    if (bf)
-        reinterpret_cast<unsigned short*>(dst)[dst_e] =
-            a.prec == NR_PREC_FP16 ? __builtin_bit_cast(unsigned short, static_cast<_Float16>(v)) : bf16_bits(v);
+    pack_store(a, l, bwd, o.dst_e,
+               o.col >= 0 ? a.params[a.w_off[l] + static_cast<int64_t>(o.row) * a.in[l] + o.col] : 0.f);
+}
+
+// ------------------------------------------------ positional-encoding window ----
+// A per-frequency weight w_k on an encoder's sin / cos columns (coarse-to-fine
+// registration) is folded into the weights that read them: W . (s * gamma) = (W * s) . gamma
+// with s = 1 on the 3 raw columns and w[(c - 3) / 6] on encoding column c.  The forward
+// and the input gradients read W only through the images, so the MLP kernels run
+// unchanged on folded images; their dW is dL/d(W * s), which window_grad_kernel scales
+// by s into dL/dW.  A window pointer may be null: all ones.
+__device__ __forceinline__ float window_scale(const float* w, int c) { return (w && c >= 3) ? w[(c - 3) / 6] : 1.0f; }
+
+// The encoding segments of the plan: layer 0 and the layer after each skip (x_enc,
+// which = 0), dir_linear (d_enc, which = 1).
+struct WindowArgs {
+    const float* w[2];
+    int n;
+    int layer[kMaxMfmaLayers], seg[kMaxMfmaLayers], blk0[kMaxMfmaLayers], which[kMaxMfmaLayers];
+    int64_t cum[kMaxMfmaLayers + 1];  // fold: image elements; grad: rows x width
+};
+
+// Rewrites the image elements of the encoding segments' k blocks (W) / row blocks (W^T)
+// from params, scaled: the elements mlp_pack_kernel writes there, through its index maps.
+__global__ void mlp_fold_window_kernel(PackArgs a, WindowArgs f) {
+    const int64_t g = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= f.cum[f.n]) return;
+    int j = 0;
+    while (g >= f.cum[j + 1]) ++j;
+    const int l = f.layer[j], sg = f.seg[j], sb = a.seg_blk[l][sg];
+    const int64_t img = (f.cum[j + 1] - f.cum[j]) / 2;  // NB x sb blocks of 1024 elements
+    int64_t r = g - f.cum[j];
+    const bool bwd = r >= img;
+    if (bwd) r -= img;
+    const int q = static_cast<int>(r / 1024);
+    const int nb = q / sb, kb = f.blk0[j] + q % sb;  // output block, input block of the layer
+    int64_t blk;
+    if (!bwd)
+        blk = a.prec != NR_PREC_FP32 ? static_cast<int64_t>(nb) * a.KB[l] + kb : static_cast<int64_t>(kb) * a.NB[l] + nb;
     else
-        reinterpret_cast<float*>(dst)[dst_e] = v;
+        blk = static_cast<int64_t>(nb) * a.KB[l] + (kb - a.bwd_rot[l] + a.KB[l]) % a.KB[l];
+    const PackLoc o = pack_locate(a, l, blk * 1024 + r % 1024, bwd);
+    if (o.col < 0) return;  // padding stays zero
+    const float v = a.params[a.w_off[l] + static_cast<int64_t>(o.row) * a.in[l] + o.col];
+    pack_store(a, l, bwd, o.dst_e, v * window_scale(f.w[f.which[j]], o.col - a.seg_col0[l][sg]));
+}
+
+struct WindowGradArgs {
+    float* g;
+    int64_t w_off[kMaxMfmaLayers];
+    int in[kMaxMfmaLayers], col0[kMaxMfmaLayers], width[kMaxMfmaLayers];
+};
+
+__global__ void window_grad_kernel(WindowGradArgs a, WindowArgs f) {
+    const int64_t g = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= f.cum[f.n]) return;
+    int j = 0;
+    while (g >= f.cum[j + 1]) ++j;
+    const float* w = f.w[f.which[j]];
+    const int64_t r = g - f.cum[j];
+    const int c = static_cast<int>(r % a.width[j]);
+    if (!w || c < 3) return;
+    a.g[a.w_off[j] + (r / a.width[j]) * a.in[j] + a.col0[j] + c] *= w[(c - 3) / 6];
 }
 
 // 16-bit dX-chain images (pk_bwdr): for layers l >= 1, A[i][k] = W[32 ob + k][hcol0 +
@@ -279,10 +358,7 @@ __global__ void __launch_bounds__(kSumsqThreads) adam_multi_kernel(AdamMultiArgs
 
 namespace {
 
-// nr_mlp_pack's four kernels; IDX: their index mode, filling the destination table
-template <bool IDX>
-int launch_pack_t(const MlpPlan& p, const float* params, void* packed, PackIdx t, hipStream_t s) {
-    const char* what = IDX ? "nr_mlp_pack_table" : "nr_mlp_pack";
+PackArgs pack_args(const MlpPlan& p, const float* params, void* packed) {
     PackArgs a;
     std::memset(&a, 0, sizeof(a));
     a.params = params;
@@ -308,6 +384,33 @@ int launch_pack_t(const MlpPlan& p, const float* params, void* packed, PackIdx t
         const int64_t elems = static_cast<int64_t>(d.NB) * d.KB * 1024;  // 32x32 elements per block
         a.cum[l + 1] = a.cum[l] + 2 * elems;
     }
+    return a;
+}
+
+// the plan's encoding segments (WindowArgs without its element counts)
+WindowArgs window_segments(const MlpPlan& p, const float* w_pos, const float* w_dir) {
+    WindowArgs f;
+    std::memset(&f, 0, sizeof(f));
+    f.w[0] = w_pos;
+    f.w[1] = w_dir;
+    auto add = [&](int l, int sg, int which) {
+        f.layer[f.n] = l;
+        f.seg[f.n] = sg;
+        f.which[f.n] = which;
+        for (int s = 0; s < sg; ++s) f.blk0[f.n] += p.lin[l].seg[s].blocks;
+        ++f.n;
+    };
+    for (int i = 0; i < p.n_layers; ++i)
+        if (i == 0 || is_skip(p, i - 1)) add(i, 0, 0);
+    if (p.use_vd) add(p.n_layers + 1, 1, 1);
+    return f;
+}
+
+// nr_mlp_pack's four kernels; IDX: their index mode, filling the destination table
+template <bool IDX>
+int launch_pack_t(const MlpPlan& p, const float* params, void* packed, PackIdx t, hipStream_t s) {
+    const char* what = IDX ? "nr_mlp_pack_table" : "nr_mlp_pack";
+    const PackArgs a = pack_args(p, params, packed);
     const int64_t total = a.cum[p.n_lin];
     hipLaunchKernelGGL(mlp_pack_kernel<IDX>, dim3(static_cast<unsigned>(ceil_div_ll(total, 256))), dim3(256), 0, s, a, t);
     NR_LAUNCH_CHECK(what);
@@ -384,6 +487,39 @@ int launch_pack_t(const MlpPlan& p, const float* params, void* packed, PackIdx t
 
 int launch_pack(const MlpPlan& p, const float* params, void* packed, PackIdx t, bool idx, hipStream_t s) {
     return idx ? launch_pack_t<true>(p, params, packed, t, s) : launch_pack_t<false>(p, params, packed, t, s);
+}
+
+int launch_fold_window(const MlpPlan& p, const float* params, void* packed, const float* w_pos, const float* w_dir,
+                       hipStream_t s) {
+    const PackArgs a = pack_args(p, params, packed);
+    WindowArgs f = window_segments(p, w_pos, w_dir);
+    for (int j = 0; j < f.n; ++j) {
+        const LinearDesc& d = p.lin[f.layer[j]];
+        f.cum[j + 1] = f.cum[j] + 2 * static_cast<int64_t>(d.NB) * d.seg[f.seg[j]].blocks * 1024;
+    }
+    if (f.cum[f.n] == 0) return NR_OK;
+    hipLaunchKernelGGL(mlp_fold_window_kernel, dim3(static_cast<unsigned>(ceil_div_ll(f.cum[f.n], 256))), dim3(256), 0,
+                       s, a, f);
+    return check_launch("nr_mlp_fold_window");
+}
+
+int launch_window_grad(const MlpPlan& p, const float* w_pos, const float* w_dir, float* g_params, hipStream_t s) {
+    WindowArgs f = window_segments(p, w_pos, w_dir);
+    WindowGradArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.g = g_params;
+    for (int j = 0; j < f.n; ++j) {
+        const LinearDesc& d = p.lin[f.layer[j]];
+        a.w_off[j] = d.w_off;
+        a.in[j] = d.in;
+        a.col0[j] = d.seg[f.seg[j]].col0;
+        a.width[j] = d.seg[f.seg[j]].width;
+        f.cum[j + 1] = f.cum[j] + static_cast<int64_t>(d.out) * a.width[j];
+    }
+    if (f.cum[f.n] == 0) return NR_OK;
+    hipLaunchKernelGGL(window_grad_kernel, dim3(static_cast<unsigned>(ceil_div_ll(f.cum[f.n], 256))), dim3(256), 0, s,
+                       a, f);
+    return check_launch("nr_mlp_window_grad");
 }
 
 int launch_adam_multi(const AdamMultiArgs& a, int grid, int nspan, hipStream_t s) {

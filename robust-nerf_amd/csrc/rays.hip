@@ -470,6 +470,49 @@ __global__ void pe_bwd_kernel(const float* x, int64_t M, int C, int L, int inc, 
     gx[p] = acc;
 }
 
+// The windowed encoding (coarse-to-fine registration): frequency k's sin and cos times
+// w[k], read from device memory (w null: all ones); the raw input block is not weighted.
+__global__ void pe_windowed_kernel(const float* x, int64_t M, int C, int L, int inc, int logs, const float* w,
+                                   float* out) {
+    const int D = inc + 2 * L;
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p >= M * C * D) return;
+    const int64_t m = p / (C * D);
+    const int col = static_cast<int>(p % (C * D));
+    const int blk = col / C, c = col % C;
+    const float v = x[m * C + c];
+    float r;
+    if (inc && blk == 0) {
+        r = v;
+    } else {
+        const int q = blk - inc;
+        const float f = pe_freq(q >> 1, L, logs);
+        r = (q & 1) ? cosf(f * v) : sinf(f * v);
+        if (w) r *= w[q >> 1];
+    }
+    out[p] = r;
+}
+
+__global__ void pe_windowed_bwd_kernel(const float* x, int64_t M, int C, int L, int inc, int logs, const float* w,
+                                       const float* g, float* gx) {
+    const int D = inc + 2 * L;
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p >= M * C) return;
+    const int64_t m = p / C;
+    const int c = static_cast<int>(p % C);
+    const float v = x[p];
+    const float* gr = g + m * C * D;
+    float acc = inc ? gr[c] : 0.f;
+    for (int k = 0; k < L; ++k) {
+        const float f = pe_freq(k, L, logs);
+        const float a = f * v;
+        const float wk = w ? w[k] : 1.0f;
+        acc += wk * (gr[(inc + 2 * k) * C + c] * (cosf(a) * f));
+        acc += wk * (gr[(inc + 2 * k + 1) * C + c] * (-sinf(a) * f));
+    }
+    gx[p] = acc;
+}
+
 // ---------------------------------------------------------------- glue ----
 __global__ void expand_viewdirs_kernel(const float* rd, int B, int S, float* out) {
     const int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -681,6 +724,28 @@ int nr_positional_encoding_bwd(const float* x, int64_t M, int C, int L, int inc,
     hipLaunchKernelGGL(pe_bwd_kernel, dim3(static_cast<unsigned>(ceil_div_ll(n, 256))), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, M, C, L, inc, logs, g, gx);
     NR_LAUNCH_CHECK("nr_positional_encoding_bwd");
+    return NR_OK;
+}
+
+int nr_positional_encoding_windowed(const float* x, int64_t M, int C, int L, int inc, int logs, const float* w,
+                                    float* out, nr_stream_t stream) {
+    NR_REQUIRE(x && out && M >= 0 && C > 0 && L >= 0, "nr_positional_encoding_windowed: bad arguments");
+    const int64_t n = M * C * (inc + 2 * L);
+    if (n == 0) return NR_OK;
+    hipLaunchKernelGGL(pe_windowed_kernel, dim3(static_cast<unsigned>(ceil_div_ll(n, 256))), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), x, M, C, L, inc, logs, w, out);
+    NR_LAUNCH_CHECK("nr_positional_encoding_windowed");
+    return NR_OK;
+}
+
+int nr_positional_encoding_windowed_bwd(const float* x, int64_t M, int C, int L, int inc, int logs, const float* w,
+                                        const float* g, float* gx, nr_stream_t stream) {
+    NR_REQUIRE(x && g && gx && M >= 0 && C > 0 && L >= 0, "nr_positional_encoding_windowed_bwd: bad arguments");
+    const int64_t n = M * C;
+    if (n == 0) return NR_OK;
+    hipLaunchKernelGGL(pe_windowed_bwd_kernel, dim3(static_cast<unsigned>(ceil_div_ll(n, 256))), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), x, M, C, L, inc, logs, w, g, gx);
+    NR_LAUNCH_CHECK("nr_positional_encoding_windowed_bwd");
     return NR_OK;
 }
 

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "nr_stratified_sample": (c_i, [c_vp, c_vp, c_vp, c_f, c_f, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     "nr_positional_encoding": (c_i, [c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp, c_vp]),
     "nr_positional_encoding_bwd": (c_i, [c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp]),
+    "nr_positional_encoding_windowed": (c_i, [c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp]),
+    "nr_positional_encoding_windowed_bwd": (c_i, [c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     "nr_sample_pdf": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp]),
     "nr_sample_hierarchical": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     "nr_composite_fwd": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -95,6 +97,8 @@ _SIGNATURES = {
     "nr_mlp_saved_bytes": (c_i64, [_cfg_p, c_i64]),
     "nr_mlp_workspace_bytes": (c_i64, [_cfg_p, c_i64]),
     "nr_mlp_pack": (c_i, [_cfg_p, c_vp, c_vp, c_vp]),
+    "nr_mlp_fold_window": (c_i, [_cfg_p, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "nr_mlp_window_grad": (c_i, [_cfg_p, c_vp, c_vp, c_vp, c_vp]),
     "nr_mlp_forward": (c_i, [_cfg_p, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "nr_mlp_backward": (c_i, [_cfg_p, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_vp]),

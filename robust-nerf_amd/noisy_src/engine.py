@@ -319,6 +319,7 @@ class GraphedTrainer:
     def __init__(self, trainer: "Trainer", rays_o: torch.Tensor, rays_d: torch.Tensor, target_rgb: torch.Tensor,
                  t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None, warmup: int = 2):
         self.trainer = trainer
+        self._refuse_window()
         opt = trainer.optimizer
         self._adam = _AdamSchedule(opt, trainer.scheduler, rays_o.device, "trainer")
         self.static = [t.detach().clone() for t in (rays_o, rays_d, target_rgb)]
@@ -371,6 +372,14 @@ class GraphedTrainer:
         opt.device_sched = None
         self._bound = self._bound_buffers()
 
+    def _refuse_window(self) -> None:
+        # a replay rewrites the images' encoding columns unfolded behind the host's back,
+        # and this class does not stage window weights: only GraphedPoseTrainer does
+        for n in (self.trainer.model_coarse, self.trainer.model_fine):
+            if n is not None and n._pe_window.on:
+                raise ValueError("GraphedTrainer does not support a positional-encoding window (NeRF.set_pe_window): "
+                                 "use the eager Trainer, or GraphedPoseTrainer")
+
     def _draw(self) -> None:
         for t in self._predraw:
             t.uniform_()  # torch.rand(shape) of the eager step, into the static buffer
@@ -414,6 +423,7 @@ class GraphedTrainer:
         if self._predraw and t_rand is None:
             self._draw()
         self._check_bound()
+        self._refuse_window()
         self._adam.write_next()
         self.graph.replay()
         self._adam.advance()
@@ -440,11 +450,18 @@ class PoseTrainer:
     Before the pose-optimisation delay (``optimize_poses=False``) the poses enter the
     step detached: the reference lets their gradient accumulate unused until the first
     optimising step's ``zero_grad``, so skipping it changes
-    nothing and saves the MLP's input-gradient pass."""
+    nothing and saves the MLP's input-gradient pass.
+
+    ``pe_schedule`` (optional) makes the positional encoding coarse-to-fine (BARF): a
+    callable ``(iteration, num_freqs) -> num_freqs weights``; a ``step`` that is given
+    its ``iteration`` sets both networks' windows from it first (``NeRF.set_pe_window``,
+    the position and the direction encoder each with its own frequency count)."""
 
     def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,
                  lr: float = 5e-4, pose_lr: float = 1e-4, lr_decay: int = 250,
-                 rotation_reg_weight: float = 0.01, translation_reg_weight: float = 0.001, process_group=None):
+                 rotation_reg_weight: float = 0.01, translation_reg_weight: float = 0.001, process_group=None,
+                 pe_schedule=None):
+        self.pe_schedule = pe_schedule
         self.model_coarse, self.model_fine = model_coarse, model_fine
         self.camera_params, self.pixel_sampler, self.render_config = camera_params, pixel_sampler, render_config
         self.coarse = list(model_coarse.parameters())
@@ -464,9 +481,21 @@ class PoseTrainer:
                 if net is not None:
                     net._grad_ready_hook = self.reducer.launch
 
+    def set_pe_windows(self, iteration: int) -> None:
+        """Both networks' windows of ``iteration`` under ``pe_schedule`` (no-op without one)."""
+        if self.pe_schedule is None:
+            return
+        for net in (self.model_coarse, self.model_fine):
+            if net is not None:
+                mc = net.config
+                net.set_pe_window(self.pe_schedule(iteration, mc.pos_freqs),
+                                  self.pe_schedule(iteration, mc.dir_freqs) if mc.use_view_dirs else None)
+
     def step(self, pixel_batch, optimize_poses: bool = True, t_rand: Optional[torch.Tensor] = None,
-             u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+             u: Optional[torch.Tensor] = None, iteration: Optional[int] = None) -> Dict[str, torch.Tensor]:
         cam = self.camera_params
+        if iteration is not None:
+            self.set_pe_windows(iteration)
         optimize_poses = optimize_poses and self.optimizer_poses is not None
         self.optimizer_nerf.zero_grad(set_to_none=True)
         if optimize_poses:
@@ -619,6 +648,10 @@ class GraphedPoseTrainer:
     replay; the Adam step counters and both LambdaLRs advance on the host exactly as in
     ``PoseTrainer.step`` (the pose optimizer's only on optimising steps).
 
+    A coarse-to-fine window (``PoseTrainer.pe_schedule``, or ``NeRF.set_pe_window`` between
+    steps) lives in each network's persistent window tensor, which the captured fold and
+    gradient-scaling launches read: it is written before a replay, never inside the graph.
+
     Every call of ``step`` is one training step of the caller's sequence.  The first
     ``warmup`` calls of a shape run eagerly (on the static buffers); so does any call
     while that shape's Adam state does not exist yet -- the optimising graph can only be
@@ -681,6 +714,9 @@ class GraphedPoseTrainer:
         tr = self.trainer
         nets = [n for n in (tr.model_coarse, tr.model_fine) if n is not None]
         ts = [t for n in nets for t in (n._packed, n._table, n._flat) if t is not None]
+        # a captured step folds the window tensors it saw (or none): both must still hold
+        ts += [w for n in nets if n._flat is not None for w in n._pe_window.device_weights(n._flat.device)
+               if w is not None]
         ts += list(tr.camera_params.parameters())
         for s in self._scheds(optimizing):
             for m, v in s.optimizer._flat_state.values():
@@ -691,8 +727,8 @@ class GraphedPoseTrainer:
         now = self._bound_buffers(optimizing)
         if len(now) != len(bound) or any(a is not b or pa != pb for (a, pa), (b, pb) in zip(now, bound)):
             raise RuntimeError("GraphedPoseTrainer: a buffer the captured graph writes was replaced (packed images, "
-                               "pack table, parameters, poses or Adam state, e.g. by a checkpoint load); "
-                               "build a new GraphedPoseTrainer")
+                               "pack table, parameters, poses or Adam state, e.g. by a checkpoint load), or a "
+                               "positional-encoding window was added or removed; build a new GraphedPoseTrainer")
 
     def _capture(self, optimizing: bool):
         tr = self.trainer
@@ -721,9 +757,10 @@ class GraphedPoseTrainer:
         return entry
 
     def step(self, pixel_batch=None, optimize_poses: bool = True, t_rand: Optional[torch.Tensor] = None,
-             u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+             u: Optional[torch.Tensor] = None, iteration: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """One training step on this batch (copied into the static buffers; None, or the
-        batch ``sample_batch(out=self.static)`` returned: the buffers as they are).  Returns
+        batch ``sample_batch(out=self.static)`` returned: the buffers as they are).
+        ``iteration`` sets the windows of ``PoseTrainer.pe_schedule`` first.  Returns
         the metrics of the graph it replayed (device tensors that every replay of that
         graph overwrites).  Eager ``trainer.step`` calls may be interleaved (same state)."""
         if self._predraw and (t_rand is None) != (u is None) and len(self._predraw) == 2:
@@ -752,6 +789,14 @@ class GraphedPoseTrainer:
         if self._predraw and t_rand is None:
             for t in self._predraw:
                 t.uniform_()  # torch.rand(shape) of the eager step, into the static buffer
+        if iteration is not None:
+            self.trainer.set_pe_windows(iteration)
+        nets = [n for n in (self.trainer.model_coarse, self.trainer.model_fine) if n is not None]
+        for n in nets:
+            if n._flat is not None:
+                # the window tensors' pending values go out here, stream-ordered before the
+                # replay (as _AdamSchedule.write_next's pair), and never inside a capture
+                n._pe_window.device_weights(n._flat.device)
         entry = self._graphs.get(optimizing)
         if entry is None:
             if self._eager_steps[optimizing] < self.warmup or not all(s.ready() for s in self._scheds(optimizing)):
@@ -767,6 +812,9 @@ class GraphedPoseTrainer:
         graph.replay()
         for s in scheds:
             s.advance()
+        for n in nets:
+            # the replayed Adam rewrote the images' encoding columns unfolded, unseen by the host
+            n._fold_key = None
         return out
 
 

@@ -43,7 +43,8 @@ from .train import render_image
 def load_checkpoint(checkpoint_path: Path, device: str = "cuda", precision: Optional[str] = None) -> tuple:
     """Reference inference.py:33-72 -> (renderer, config dict, iteration).  Loads with
     ``weights_only=True``: a checkpoint is tensors, dicts, lists and scalars only.
-    ``precision`` overrides the MLP operand precision stored with the checkpoint."""
+    ``precision`` overrides the MLP operand precision stored with the checkpoint; a
+    positional-encoding window stored with it (``mi355x.pe_window``) is applied."""
     ckpt = torch.load(checkpoint_path, map_location=device, weights_only=True)
     cfg = ckpt.get("config", {})
     model_cfg = ModelConfig(**cfg.get("model", {}))
@@ -58,6 +59,13 @@ def load_checkpoint(checkpoint_path: Path, device: str = "cuda", precision: Opti
         fine = NeRF(model_cfg).to(device)
         fine.load_state_dict(ckpt["model_fine"])
         fine.eval()
+    window = ckpt.get("mi355x", {}).get("pe_window")
+    if window is not None:
+        # saved while a coarse-to-fine window was active (train_pose_opt --c2f): the
+        # weights were trained against that encoding, so they render with it
+        for net in (coarse, fine):
+            if net is not None:
+                net.set_pe_window(window.get("pos"), window.get("dir"))
     return NeRFRenderer(coarse, fine, render_cfg), cfg, ckpt.get("iteration", 0)
 
 

@@ -42,6 +42,8 @@ class PositionalEncoding(nn.Module):
         else:
             freq_bands = torch.linspace(1.0, 2.0 ** (num_freqs - 1), num_freqs)
         self.register_buffer("freq_bands", freq_bands)
+        # (window, "pos" | "dir"): the owning NeRF's per-frequency weights (set_pe_window)
+        self._window_src = None
 
     @property
     def output_dim(self) -> int:
@@ -51,7 +53,102 @@ class PositionalEncoding(nn.Module):
         return dim
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return ops.positional_encoding(x, self.num_freqs, self.include_input, self.log_sampling)
+        window = None
+        if self._window_src is not None and x.is_cuda:
+            window = self._window_src[0].device_weights(x.device)[0 if self._window_src[1] == "pos" else 1]
+        return ops.positional_encoding(x, self.num_freqs, self.include_input, self.log_sampling, window=window)
+
+
+class _PEWindow:
+    """A network's coarse-to-fine window: a weight per frequency of each encoder
+    (``NeRF.set_pe_window``).  The weights live in ONE persistent device tensor
+    ([pos_freqs | dir_freqs] floats, ones where a half is not windowed) that is only ever
+    rewritten in place, through a pinned staging ring, so a captured hipGraph that reads
+    it stays valid and setting a window does not synchronise the host.  ``version``
+    counts the updates: the fold of the packed images is keyed on it."""
+
+    RING = 64
+
+    def __init__(self, pos_freqs: int, dir_freqs: int) -> None:
+        self.L, self.Ld = pos_freqs, dir_freqs
+        self.active = (False, False)  # which halves carry a window
+        self.version = 0
+        self._host = torch.ones(pos_freqs + dir_freqs, dtype=torch.float32)
+        self._dev: Optional[torch.Tensor] = None
+        self._views = None  # (_dev[:L], _dev[L:])
+        self._dev_version = -1
+        self._ring: Optional[torch.Tensor] = None
+        self._ring_ev = [None] * self.RING
+        self._k = 0
+
+    def __deepcopy__(self, memo):
+        c = _PEWindow(self.L, self.Ld)  # its own device tensor, made on first use
+        if self.on:
+            c.set(*self.host_weights())
+        return c
+
+    def __getstate__(self):
+        return self.__deepcopy__({}).__dict__  # the weights; no device tensor, ring or events
+
+    @property
+    def on(self) -> bool:
+        return self.active[0] or self.active[1]
+
+    def set(self, pos, dir) -> None:
+        host = torch.ones_like(self._host)
+        dev_src = []
+        for lo, n, w in ((0, self.L, pos), (self.L, self.Ld, dir)):
+            if w is None:
+                continue
+            if isinstance(w, torch.Tensor) and w.is_cuda:
+                dev_src.append((lo, n, w.detach().to(torch.float32).reshape(-1)))
+            else:
+                host[lo:lo + n] = torch.as_tensor(w, dtype=torch.float64).reshape(-1).to(torch.float32)
+        self._host = host
+        self.active = (pos is not None, dir is not None)
+        self.version += 1
+        if self._dev is not None and self.on:
+            self._write(dev_src)
+        elif dev_src:  # no device tensor yet: keep the values on the host until first use
+            for lo, n, w in dev_src:
+                self._host[lo:lo + n] = w.cpu()
+
+    def _write(self, dev_src=()) -> None:
+        """Stage the host weights into the device tensor, stream-ordered, in place."""
+        if self._ring is None:
+            self._ring = torch.ones(self.RING, self._host.numel(), dtype=torch.float32).pin_memory()
+        slot = self._k % self.RING
+        if self._ring_ev[slot] is not None:
+            self._ring_ev[slot].synchronize()  # the copy that read this slot has run
+        self._ring[slot].copy_(self._host)
+        with torch.cuda.device(self._dev.device):
+            self._dev.copy_(self._ring[slot], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self._ring_ev[slot] = ev
+        self._k += 1
+        for lo, n, w in dev_src:
+            self._dev[lo:lo + n].copy_(w)
+        self._dev_version = self.version
+
+    def device_weights(self, device) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """(w_pos, w_dir) on ``device``: views of the persistent tensor, None for a half
+        without a window."""
+        if not self.on:
+            return None, None
+        if self._dev is None or self._dev.device != device:
+            self._dev = torch.ones(self.L + self.Ld, device=device, dtype=torch.float32)
+            self._views = (self._dev[:self.L], self._dev[self.L:])  # the same objects at every call
+            self._dev_version = -1
+        if self._dev_version != self.version:
+            self._write()
+        return (self._views[0] if self.active[0] else None, self._views[1] if self.active[1] else None)
+
+    def host_weights(self) -> Tuple[Optional[List[float]], Optional[List[float]]]:
+        """The weights as lists (None for a half without a window); reads the device
+        tensor when device weights were given."""
+        src = self._host if self._dev is None or self._dev_version != self.version else self._dev.cpu()
+        return (src[:self.L].tolist() if self.active[0] else None, src[self.L:].tolist() if self.active[1] else None)
 
 
 # NR_MLP_DENSE_BACKWARD=1 runs every 32-sample tile through the backward (the dense
@@ -84,6 +181,16 @@ class _MLPFunction(torch.autograd.Function):
         rgb = torch.empty(M, 3, device=xc.device, dtype=torch.float32)
         sigma = torch.empty(M, 1, device=xc.device, dtype=torch.float32)
         training = any(ctx.needs_input_grad)
+        w_pos, w_dir = net._pe_window.device_weights(xc.device)
+        if w_pos is not None or w_dir is not None:
+            # coarse-to-fine window: folded into the images' encoding columns.  A training
+            # forward always folds (the fused Adam of the step before rewrote those columns
+            # unfolded, and a graph replay does so without the host seeing it); an inference
+            # forward only when the images are not folded with the current weights
+            fold_key = (net._packed_key, net._pe_window.version)
+            if training or net._fold_key != fold_key:
+                call("nr_mlp_fold_window", cfg, ptr(flat), ptr(w_pos), ptr(w_dir), ptr(packed), _hip.stream_ptr())
+                net._fold_key = fold_key
         saved = None
         if training and M > 0:
             saved = torch.empty(int(_hip.load().nr_mlp_saved_bytes(cfg, M)), device=xc.device, dtype=torch.uint8)
@@ -92,14 +199,14 @@ class _MLPFunction(torch.autograd.Function):
         if training:
             ctx.save_for_backward(xc, dc if dc is not None else xc.new_empty(0), rgb, sigma)
             ctx.has_d = dc is not None
-            ctx.keep = (net, saved, packed, flat)
+            ctx.keep = (net, saved, packed, flat, w_pos, w_dir)
             ctx.shapes = [p.shape for p in params]
         return rgb, sigma
 
     @staticmethod
     def backward(ctx, g_rgb, g_sigma):
         xc, dc, rgb, sigma = ctx.saved_tensors
-        net, saved, packed, flat = ctx.keep
+        net, saved, packed, flat, w_pos, w_dir = ctx.keep
         cfg = ctypes.byref(net._nr_cfg)
         M = xc.shape[0]
         dev = xc.device
@@ -117,6 +224,9 @@ class _MLPFunction(torch.autograd.Function):
             call("nr_mlp_backward_dx", *args, tag=tag)
             call("nr_mlp_backward_dw", cfg, M, ptr(saved), ptr(ws), st, tag=tag)
             call("nr_mlp_backward_reduce", cfg, M, ptr(ws), ptr(gflat), st, tag=tag)
+            if w_pos is not None or w_dir is not None:
+                # the images were folded: dL/d(W * s) -> dL/dW on the encoding columns
+                call("nr_mlp_window_grad", cfg, ptr(w_pos), ptr(w_dir), ptr(gflat), st)
             if net._tile_counts is not None:
                 # diagnostics (bench.py): the active-tile count this backward ran on
                 off = int(_hip.load().nr_mlp_active_tiles_offset(cfg, M))
@@ -176,6 +286,11 @@ class NeRF(nn.Module):
         self.config = config
         self.pos_encoder = PositionalEncoding(num_freqs=config.pos_freqs, include_input=True)
         self.dir_encoder = PositionalEncoding(num_freqs=config.dir_freqs, include_input=True)
+        # coarse-to-fine window (set_pe_window): not a buffer, state_dict() keeps the reference's keys
+        self._pe_window = _PEWindow(config.pos_freqs, config.dir_freqs)
+        self.pos_encoder._window_src = (self._pe_window, "pos")
+        self.dir_encoder._window_src = (self._pe_window, "dir")
+        self._fold_key = None  # (packed key, window version) the images are folded for
         pos_dim = 3 * self.pos_encoder.output_dim
         dir_dim = 3 * self.dir_encoder.output_dim
         self.pts_linears = nn.ModuleList()
@@ -224,6 +339,35 @@ class NeRF(nn.Module):
             t = torch.zeros(4, device=device, dtype=torch.int32)
             self._tickets[device] = t
         return t
+
+    # -- coarse-to-fine positional encoding ------------------------------------
+    def set_pe_window(self, pos=None, dir=None) -> None:
+        """Weight frequency k of the position encoder by ``pos[k]`` and of the direction
+        encoder by ``dir[k]`` (BARF's coarse-to-fine window; the raw input columns are
+        never weighted): tensors or float sequences of length ``pos_freqs`` /
+        ``dir_freqs``, each None for all ones.  ``set_pe_window(None, None)`` removes the
+        window.  The fused MLP, ``pos_encoder`` and ``dir_encoder`` all use the weights;
+        they get no gradient and are not part of ``state_dict()``.  The weights are
+        written in place into one persistent device tensor, so a captured step reads
+        the values of its replay."""
+        for name, w, n in (("pos", pos, self.config.pos_freqs), ("dir", dir, self.config.dir_freqs)):
+            if w is None:
+                continue
+            if name == "dir" and not self.config.use_view_dirs:
+                raise ValueError("set_pe_window: dir must be None for a model without view directions")
+            got = w.numel() if isinstance(w, torch.Tensor) else len(w)
+            if got != n:
+                raise ValueError(f"set_pe_window: {name} needs {n} weights ({name}_freqs), got {got}")
+        was_on = self._pe_window.on
+        self._pe_window.set(pos, dir)
+        if was_on and not self._pe_window.on:
+            self._packed_key = None  # the images may be folded: the next forward re-packs
+        if not self._pe_window.on:
+            self._fold_key = None
+
+    def pe_window(self) -> Tuple[Optional[List[float]], Optional[List[float]]]:
+        """The current window as (pos, dir) lists of floats, None where not windowed."""
+        return self._pe_window.host_weights()
 
     # -- flat parameter buffer -------------------------------------------------
     @property

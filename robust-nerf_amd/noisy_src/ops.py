@@ -289,9 +289,43 @@ class _PosEnc(torch.autograd.Function):
         return gx, None, None, None
 
 
-def positional_encoding(x, num_freqs, include_input=True, log_sampling=True):
+class _PosEncWindowed(torch.autograd.Function):
+    """The encoding with a per-frequency weight read from device memory (``window``: L
+    floats; its values at the time each kernel runs, so it may be rewritten in place)."""
+
+    @staticmethod
+    def forward(ctx, x, L, include_input, log_sampling, window):
+        xc = _c(x)
+        C = xc.shape[-1]
+        M = xc.numel() // C
+        D = (1 if include_input else 0) + 2 * L
+        out = torch.empty(*xc.shape[:-1], C * D, device=xc.device, dtype=_f32)
+        call("nr_positional_encoding_windowed", ptr(xc), M, C, L, int(include_input), int(log_sampling), ptr(window),
+             ptr(out), _stream())
+        ctx.save_for_backward(xc, window)
+        ctx.args = (L, include_input, log_sampling)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, window = ctx.saved_tensors
+        L, inc, logs = ctx.args
+        C = xc.shape[-1]
+        gx = torch.empty_like(xc)
+        call("nr_positional_encoding_windowed_bwd", ptr(xc), xc.numel() // C, C, L, int(inc), int(logs), ptr(window),
+             ptr(_c(g)), ptr(gx), _stream())
+        return gx, None, None, None, None
+
+
+def positional_encoding(x, num_freqs, include_input=True, log_sampling=True, window=None):
+    """``window`` (optional, (num_freqs,) fp32 on x's device): a weight per frequency on
+    its sin / cos columns (coarse-to-fine registration); it gets no gradient."""
     _check(x)
-    return _PosEnc.apply(x, num_freqs, include_input, log_sampling)
+    if window is None:
+        return _PosEnc.apply(x, num_freqs, include_input, log_sampling)
+    if window.dtype != _f32 or window.numel() != num_freqs or window.device != x.device:
+        raise ValueError(f"positional_encoding: window must be {num_freqs} fp32 weights on {x.device}")
+    return _PosEncWindowed.apply(x, num_freqs, include_input, log_sampling, window.detach())
 
 
 # ---------------------------------------------------------------- A8 ---------

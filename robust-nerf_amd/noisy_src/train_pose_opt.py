@@ -23,6 +23,11 @@ Joint NeRF + camera-pose training step — drop-in for ShawnnnLiu/Robust-NeRF
   (``engine.GraphedPoseTrainer``: one graph for frozen poses, one for optimising, the
   pixel batch gathered straight into their static inputs), bit-identical to eager; it
   pays below 1,024 rays per GPU.
+* ``c2f=(start, end)`` (``--c2f START END``) anneals both positional encodings coarse to
+  fine as BARF does (Lin et al., ICCV 2021): ``pe_window_weights(c2f_alpha(...))`` per
+  iteration, folded into the MLP's weight images (``NeRF.set_pe_window``).  The reference
+  lists it as future work; it is meant for ``fixed_small_angle=True``
+  (``--fixed_small_angle``), where the rotation gradients are live.
 """
 
 from __future__ import annotations
@@ -33,7 +38,7 @@ import random
 import time
 from datetime import datetime
 from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -62,6 +67,22 @@ def set_seed(seed: int) -> None:
     torch.manual_seed(seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(seed)
+
+
+def pe_window_weights(alpha: float, num_freqs: int) -> List[float]:
+    """BARF's coarse-to-fine window (Lin et al., ICCV 2021, eq. 14): the weight of
+    frequency k at progress ``alpha`` in [0, num_freqs],
+    ``w_k = (1 - cos(pi * clamp(alpha - k, 0, 1))) / 2``, in fp64."""
+    return [(1.0 - math.cos(math.pi * min(max(alpha - k, 0.0), 1.0))) / 2.0 for k in range(num_freqs)]
+
+
+def c2f_alpha(iteration: int, num_iterations: int, start: float, end: float, num_freqs: int) -> float:
+    """``alpha = L * clamp((p - start) / (end - start), 0, 1)`` with ``p = iteration /
+    num_iterations``: no frequency before ``start``, all of them from ``end`` on."""
+    if not end > start:
+        raise ValueError(f"c2f: end ({end}) must be greater than start ({start})")
+    p = iteration / num_iterations
+    return num_freqs * min(max((p - start) / (end - start), 0.0), 1.0)
 
 
 class CameraPoseParameters(nn.Module):
@@ -208,6 +229,11 @@ def render_image_with_pose(model_coarse: NeRF, model_fine: Optional[NeRF], pose:
             "acc": torch.cat(acc).reshape(H, W)}
 
 
+def _window_dict(net: NeRF) -> Optional[Dict[str, Optional[List[float]]]]:
+    pos, dir_ = net.pe_window()
+    return None if pos is None and dir_ is None else {"pos": pos, "dir": dir_}
+
+
 @torch.no_grad()
 def evaluate_with_poses(model_coarse: NeRF, model_fine: Optional[NeRF], camera_params: CameraPoseParameters,
                         val_data: BlenderData, val_indices: torch.Tensor, render_config: RenderConfig,
@@ -215,7 +241,8 @@ def evaluate_with_poses(model_coarse: NeRF, model_fine: Optional[NeRF], camera_p
                         lpips_metric=None) -> ValidationMetrics:
     """Reference train_pose_opt.py:474-545: renders the first ``num_images`` validation
     views from their GROUND-TRUTH poses (the learnable poses are the training views');
-    PNGs of the first three when a logger is given."""
+    PNGs of the first three when a logger is given.  The networks render with their
+    current positional-encoding windows (``NeRF.set_pe_window``)."""
     psnr, ssim, mse, lp = [], [], [], []
     for i, idx in enumerate(val_indices[:min(num_images, len(val_indices))]):
         idx = int(idx)
@@ -249,6 +276,9 @@ def save_checkpoint_with_poses(output_dir, iteration: int, model_coarse, model_f
             "camera_params": camera_params.state_dict(), "optimizer_nerf": optimizer_nerf.state_dict(),
             "initial_poses": camera_params.initial_poses.cpu(), "config": checkpoint_config(config),
             "mi355x": {"precision": getattr(config.model, "precision", "fp32")}}
+    window = _window_dict(model_coarse)
+    if window is not None:
+        ckpt["mi355x"]["pe_window"] = window  # both networks share the schedule
     if model_fine is not None:
         ckpt["model_fine"] = model_fine.state_dict()
     if optimizer_poses is not None:
@@ -278,7 +308,8 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                  rotation_reg_weight: float = 0.01, translation_reg_weight: float = 0.001, *,
                                  train_data: Optional[BlenderData] = None, val_data: Optional[BlenderData] = None,
                                  process_group=None, experiment_name: Optional[str] = None,
-                                 log=print, graph: bool = False) -> Dict[str, object]:
+                                 log=print, graph: bool = False, c2f: Optional[Tuple[float, float]] = None,
+                                 fixed_small_angle: bool = False) -> Dict[str, object]:
     """Reference train_pose_opt.py:613-1054 (same arguments, outputs and files).
     ``train_data`` / ``val_data`` (optional) replace the on-disk scene; ``process_group``
     makes it data parallel; ``experiment_name`` pins the generated run name (all ranks).
@@ -286,7 +317,11 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     as eager): iteration 0 runs eagerly, the frozen-pose graph is captured at the next
     iteration; the first iteration that optimises the poses runs eagerly (it creates the
     pose Adam's state) and the optimising graph is captured at the one after it.  With
-    data parallelism it needs the nccl backend."""
+    data parallelism it needs the nccl backend.
+    ``c2f=(start, end)`` windows both positional encodings coarse to fine over that
+    fraction of the run (``c2f_alpha``, ``pe_window_weights``); ``fixed_small_angle`` is
+    ``CameraPoseParameters``' (live rotation gradients at w = 0).  Neither is in the
+    reference; both default to its behaviour."""
     import torch.distributed as dist
 
     rank, world = 0, 1
@@ -297,6 +332,15 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         raise ValueError("train_with_pose_optimization(graph=True) with data parallelism needs the nccl (RCCL) "
                          "backend")
     check_run_args(config, world, train_data, val_data)
+    pe_schedule = None
+    if c2f is not None:
+        c2f = (float(c2f[0]), float(c2f[1]))
+        if not 0.0 <= c2f[0] < c2f[1]:
+            raise ValueError(f"c2f=(start, end) needs 0 <= start < end, got {c2f}")
+        n_it = config.train.num_iterations
+
+        def pe_schedule(iteration, num_freqs):
+            return pe_window_weights(c2f_alpha(iteration, n_it, c2f[0], c2f[1], num_freqs), num_freqs)
     set_seed(config.train.seed)
     device = config.train.device
     if device.startswith("cuda") and not torch.cuda.is_available():
@@ -320,7 +364,8 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                 f"translation {np.mean([e['translation_error'] for e in errs]):.4f}")
     else:
         initial_poses = gt_train_poses.clone()
-    camera_params = CameraPoseParameters(initial_poses, learn_rotation, learn_translation).to(device)
+    camera_params = CameraPoseParameters(initial_poses, learn_rotation, learn_translation,
+                                         fixed_small_angle=fixed_small_angle).to(device)
     model_coarse, model_fine = create_nerf_for(config, device)
     if logger is not None:
         logger.log_model_info(model_coarse, "model_coarse")
@@ -330,13 +375,19 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     pixel_sampler.batch_size = config.data.batch_size
     trainer = PoseTrainer(model_coarse, model_fine, camera_params, pixel_sampler, config.render, lr=config.train.lr,
                           pose_lr=pose_lr, lr_decay=config.train.lr_decay, rotation_reg_weight=rotation_reg_weight,
-                          translation_reg_weight=translation_reg_weight, process_group=process_group)
+                          translation_reg_weight=translation_reg_weight, process_group=process_group,
+                          pe_schedule=pe_schedule)
     optimizer_nerf, optimizer_poses = trainer.optimizer_nerf, trainer.optimizer_poses
     lpips_metric = LPIPSMetric(device=device) if rank == 0 else None
     if lpips_metric is not None and not lpips_metric.available:
         lpips_metric = None
     if rank == 0:
         nc = noise_config
+        extra = {}
+        if c2f is not None:
+            extra["c2f"] = list(c2f)
+        if fixed_small_angle:
+            extra["fixed_small_angle"] = True
         (output_dir / "experiment_config.json").write_text(json.dumps({
             "scene": config.data.scene_name, "experiment_name": exp_name, "init_mode": init_mode,
             "pose_optimization": {"learn_rotation": learn_rotation, "learn_translation": learn_translation,
@@ -347,7 +398,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                              "translation_noise_pct": nc.translation_noise_pct, "seed": nc.seed,
                              "has_noise": nc.has_noise} if nc else None,
             "num_iterations": config.train.num_iterations, "batch_size": config.data.batch_size,
-            "timestamp": datetime.now().isoformat(), "data_parallel_ranks": world}, indent=2))
+            "timestamp": datetime.now().isoformat(), "data_parallel_ranks": world, **extra}, indent=2))
         log(f"joint NeRF + pose optimisation: {exp_name} -> {output_dir} ({world} rank(s))")
 
     B = config.data.batch_size
@@ -388,9 +439,9 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         if graph and iteration >= 1:
             if graphed is None:  # after one eager step: the networks' Adam state exists
                 graphed = GraphedPoseTrainer(trainer, args[0], args[2], args[3], warmup=0)
-            m = graphed.step(*args)  # eager once more where the pose Adam's state is new
+            m = graphed.step(*args, iteration=iteration)  # eager once more where the pose Adam's state is new
         else:
-            m = trainer.step(*args)
+            m = trainer.step(*args, iteration=iteration)
         keys = ["loss", "loss_coarse"] + (["loss_fine"] if "loss_fine" in m else [])
         t_now = time.time()
         log_iteration(lagged.push(mean_over_ranks([m[k] for k in keys], process_group),
@@ -420,6 +471,9 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                        optimizer_nerf, optimizer_poses, config, noise_config, pose_errors=pe)
             t_prev = time.time()
     log_iteration(lagged.flush())
+    if pe_schedule is not None:
+        # the final evaluation and checkpoint: the window at the end of the schedule
+        trainer.set_pe_windows(config.train.num_iterations)
     result = {"model_coarse": model_coarse, "model_fine": model_fine, "camera_params": camera_params,
               "output_dir": output_dir, "pose_errors": camera_params.compute_pose_errors(gt_train_poses)}
     if logger is not None:
@@ -464,8 +518,8 @@ GRAPH_HELP = ("replay the joint step from hipGraphs, one for frozen poses and on
 
 
 def build_arg_parser():
-    """Reference train_pose_opt.py:1057-1142 flags (same names and defaults) plus ``--precision``
-    and ``--graph``."""
+    """Reference train_pose_opt.py:1057-1142 flags (same names and defaults) plus ``--precision``,
+    ``--graph``, ``--c2f`` and ``--fixed_small_angle``."""
     import argparse
     ap = argparse.ArgumentParser(description="Joint NeRF + camera pose optimisation (MI355X HIP path)")
     ap.add_argument("--scene", type=str, default="lego")
@@ -497,6 +551,12 @@ def build_arg_parser():
     ap.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
                     help="MLP operand precision (fp32 = the reference's numerics)")
     ap.add_argument("--graph", action="store_true", help=GRAPH_HELP)
+    ap.add_argument("--c2f", type=float, nargs=2, default=None, metavar=("START", "END"),
+                    help="coarse-to-fine positional encoding (BARF): the frequencies of both encoders are "
+                         "enabled one after another between the fractions START and END of the run")
+    ap.add_argument("--fixed_small_angle", action="store_true",
+                    help="exact Rodrigues derivative at zero rotation deltas, so the rotations learn (the "
+                         "reference blocks that gradient)")
     return ap
 
 
@@ -525,7 +585,8 @@ def main(argv=None) -> None:
     train_with_pose_optimization(cfg, noise_config, a.init_mode, a.pose_lr, a.pose_opt_delay,
                                  not a.no_learn_rotation, not a.no_learn_translation, a.rotation_reg_weight,
                                  a.translation_reg_weight, process_group=pg, experiment_name=name[0],
-                                 graph=a.graph)
+                                 graph=a.graph, c2f=tuple(a.c2f) if a.c2f is not None else None,
+                                 fixed_small_angle=a.fixed_small_angle)
     if pg is not None:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -533,7 +594,7 @@ def main(argv=None) -> None:
 
 __all__ = ["set_seed", "CameraPoseParameters", "train_step_with_poses", "render_image_with_pose",
            "evaluate_with_poses", "save_checkpoint_with_poses", "generate_experiment_name",
-           "train_with_pose_optimization", "main"]
+           "train_with_pose_optimization", "pe_window_weights", "c2f_alpha", "main"]
 
 if __name__ == "__main__":
     main()
