@@ -305,6 +305,38 @@ int nr_mlp_backward_reduce(const NrMlpConfig* cfg, int64_t M,
  * nr_mlp_backward_dx wrote (of ceil(M / 32)), or -1: the work the backward ran. */
 int64_t nr_mlp_active_tiles_offset(const NrMlpConfig* cfg, int64_t M);
 
+/* Frozen field (additive to ABI 5): the input gradients of a network whose
+ * parameters get no gradient -- a pose step against a fixed field.  The pair
+ * computes rgb / sigma and g_x / g_d bit-identical to nr_mlp_forward (with
+ * saved) and nr_mlp_backward_dx: the same products in the same order.  No
+ * parameter gradient, no dW list or count.  Caller-owned buffers, no allocation,
+ * no synchronisation, capturable.
+ *   bf16 / fp16: the forward keeps only the ReLU masks (ceil(M / 32) * (n_layers
+ *     + 1) KB: 288 B per sample for the default model, against about 5.3 KB), and
+ *     the backward stores only the dz images the input gradients read (layer 0,
+ *     the layer after each skip, dir_linear: 1.28 KB of about 4.9 KB per sample).
+ *   fp32 (parity mode, not the fast one): the backward reads the activations, so
+ *     both buffers have the training sizes and layout and the pair is
+ *     nr_mlp_forward + nr_mlp_backward_dx.
+ * saved_frozen and this workspace have layouts of their own (csrc/mlp_plan.hpp,
+ * FrozenSizes): a saved_frozen buffer must not be given to nr_mlp_backward_dx /
+ * _dw / nr_mlp_backward, nor a `saved` buffer of nr_mlp_forward to
+ * nr_mlp_backward_input.  Neither can be checked at run time.
+ * g_x / g_d: each nullable, OVERWRITTEN (exact zeros for the samples of tiles
+ * without incoming gradient, unless cfg->dense_backward).  M == 0: NR_OK.        */
+int64_t nr_mlp_frozen_saved_bytes(const NrMlpConfig* cfg, int64_t M);
+int64_t nr_mlp_frozen_workspace_bytes(const NrMlpConfig* cfg, int64_t M);
+int nr_mlp_forward_frozen(const NrMlpConfig* cfg, const void* packed,
+                          const float* params, const float* x, const float* d,
+                          int64_t M, float* rgb, float* sigma,
+                          void* saved_frozen, nr_stream_t stream);
+int nr_mlp_backward_input(const NrMlpConfig* cfg, const void* packed,
+                          const float* params, const float* x, const float* d,
+                          int64_t M, const float* rgb, const float* sigma,
+                          const void* saved_frozen, const float* g_rgb,
+                          const float* g_sigma, float* g_x, float* g_d,
+                          void* workspace, nr_stream_t stream);
+
 /* ---- A13: optimizer tail  (noisy_src/train.py:112-117, train_pose_opt.py:398-409)
  * Sum of squares of n fp32 values added into *acc (device scalar, caller-zeroed):
  * the squared global norm of torch.nn.utils.clip_grad_norm_.  A fixed-shape

@@ -52,6 +52,66 @@ void add_stream_layer(StreamDesc& sd, int nchunks, int chunk_kb, int load_kb = -
     }
 }
 
+// 16-bit forward arguments; the saved region's offsets are the caller's (training: make_sizes)
+RbmArgs rbm_args(const MlpPlan& p, const void* packed, const float* params, const float* x, const float* d, int64_t M,
+                 int64_t tiles, float* rgb, float* sigma, void* saved) {
+    RbmArgs r;
+    std::memset(&r, 0, sizeof(r));
+    r.packed = static_cast<const char*>(packed);
+    r.params = params;
+    r.x = x;
+    r.d = d;
+    r.rgb = rgb;
+    r.sigma = sigma;
+    r.saved = static_cast<char*>(saved);
+    r.M = M;
+    r.tiles = tiles;
+    r.L = p.L;
+    r.Ld = p.Ld;
+    r.n_layers = p.n_layers;
+    r.skips = p.skips;
+    r.base = p.lin[0].pk_fwd;
+    r.vhead = p.vhead;
+    r.sig_b = p.sig_b;
+    r.rgb_b = p.rgb_b;
+    r.sv_feat = p.sv_feat;
+    r.sv_denc = p.sv_denc;
+    r.sv_hc = p.sv_hc;
+    r.n_mask = p.n_mask;
+    return r;
+}
+
+// 16-bit dX chain arguments; the workspace offsets, lists and scratch tiles are the caller's
+BwdrArgs bwdr_args(const MlpPlan& p, const void* packed, int64_t M, int64_t tiles, int64_t nseg, const float* rgb,
+                   const float* sigma, const void* saved, const float* g_rgb, const float* g_sigma, char* wsb,
+                   const uint8_t* tflags, const uint32_t* blkcnt) {
+    const int n = p.n_layers;
+    BwdrArgs r;
+    std::memset(&r, 0, sizeof(r));
+    r.gscale = grad_scale(p.prec);
+    r.packed = static_cast<const char*>(packed);
+    r.rgb = rgb;
+    r.sigma = sigma;
+    r.g_rgb = g_rgb;
+    r.g_sigma = g_sigma;
+    r.saved = static_cast<const char*>(saved);
+    r.ws = wsb;
+    r.M = M;
+    r.tiles = tiles;
+    r.flags = tflags;
+    r.blk_count = blkcnt;
+    r.nseg = nseg;
+    r.n_layers = n;
+    r.base = p.lin[n + 1].pk_bwdr;
+    r.vrgb = p.vrgb;
+    r.vhead = p.vhead;
+    r.n_mask = p.n_mask;
+    r.ws_feat = p.ws_feat;
+    r.ws_dir = p.ws_dir;
+    r.ws_heads = p.ws_heads;
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -172,31 +232,9 @@ int nr_mlp_forward(const NrMlpConfig* cfg, const void* packed, const float* para
     const MlpSizes z = make_sizes(p, M);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.prec != NR_PREC_FP32) {
-        RbmArgs r;
-        std::memset(&r, 0, sizeof(r));
-        r.packed = static_cast<const char*>(packed);
-        r.params = params;
-        r.x = x;
-        r.d = d;
-        r.rgb = rgb;
-        r.sigma = sigma;
-        r.saved = static_cast<char*>(saved);
-        r.M = M;
-        r.tiles = z.tiles;
-        r.L = p.L;
-        r.Ld = p.Ld;
-        r.n_layers = p.n_layers;
-        r.skips = p.skips;
-        r.base = p.lin[0].pk_fwd;
-        r.vhead = p.vhead;
-        r.sig_b = p.sig_b;
-        r.rgb_b = p.rgb_b;
+        RbmArgs r = rbm_args(p, packed, params, x, d, M, z.tiles, rgb, sigma, saved);
         for (int t = 0; t < p.n_saved; ++t) r.sv_off[t] = z.saved_off[t];
-        r.sv_feat = p.sv_feat;
-        r.sv_denc = p.sv_denc;
-        r.sv_hc = p.sv_hc;
         r.mask_off = z.mask_off;
-        r.n_mask = p.n_mask;
         return launch_fwd_rbm(p, r, saved != nullptr, s);
     }
     FwdArgs a;
@@ -261,34 +299,12 @@ int nr_mlp_backward_dx(const NrMlpConfig* cfg, const void* packed, const float* 
     if (p.prec != NR_PREC_FP32) {
         // 16-bit: the row-block-major dX chain (mlp_bwd_rbm.inc); g_x / g_d come from a
         // separate pass over the dz images it stores (mlp_dinput_kernel)
-        BwdrArgs r;
-        std::memset(&r, 0, sizeof(r));
-        r.gscale = grad_scale(p.prec);
-        r.packed = static_cast<const char*>(packed);
-        r.rgb = rgb;
-        r.sigma = sigma;
-        r.g_rgb = g_rgb;
-        r.g_sigma = g_sigma;
-        r.saved = static_cast<const char*>(saved);
-        r.ws = wsb;
-        r.M = M;
-        r.tiles = z.tiles;
-        r.flags = tflags;
-        r.blk_count = blkcnt;
-        r.nseg = z.nseg;
+        BwdrArgs r = bwdr_args(p, packed, M, z.tiles, z.nseg, rgb, sigma, saved, g_rgb, g_sigma, wsb, tflags, blkcnt);
         r.dw_list = dwlist;
         r.count = tcount;
         r.scratch_base = z.tiles_alloc - kScratchTiles;
-        r.n_layers = n;
-        r.base = p.lin[n + 1].pk_bwdr;
-        r.vrgb = p.vrgb;
-        r.vhead = p.vhead;
         r.mask_off = z.mask_off;
-        r.n_mask = p.n_mask;
         for (int t = 0; t < p.n_ws; ++t) r.ws_off[t] = z.ws_off[t];
-        r.ws_feat = p.ws_feat;
-        r.ws_dir = p.ws_dir;
-        r.ws_heads = p.ws_heads;
         const int rc = launch_bwd_rbm(p, r, s);
         if (rc != NR_OK || !(g_x || g_d)) return rc;
         return input_grads16(p, z, r.packed, x, d, g_x, g_d, wsb, M, s);
@@ -471,6 +487,73 @@ int nr_mlp_backward_reduce(const NrMlpConfig* cfg, int64_t M, const void* worksp
     int max_rows = 1;
     for (int k = 0; k < p.n_red; ++k) max_rows = p.red[k].rows > max_rows ? p.red[k].rows : max_rows;
     return launch_dw_reduce(r, max_rows, s);
+}
+
+int64_t nr_mlp_frozen_saved_bytes(const NrMlpConfig* cfg, int64_t M) {
+    MlpPlan p;
+    if (!plan_or_error(cfg, &p) || M < 0) return -1;
+    return make_frozen_sizes(p, M).saved_bytes;
+}
+
+int64_t nr_mlp_frozen_workspace_bytes(const NrMlpConfig* cfg, int64_t M) {
+    MlpPlan p;
+    if (!plan_or_error(cfg, &p) || M < 0) return -1;
+    return make_frozen_sizes(p, M).ws_bytes;
+}
+
+int nr_mlp_forward_frozen(const NrMlpConfig* cfg, const void* packed, const float* params, const float* x,
+                          const float* d, int64_t M, float* rgb, float* sigma, void* saved_frozen,
+                          nr_stream_t stream) {
+    MlpPlan p;
+    if (!plan_or_error(cfg, &p)) return NR_EARG;
+    NR_REQUIRE(packed && params && x && rgb && sigma && saved_frozen && M >= 0, "nr_mlp_forward_frozen: null pointer");
+    NR_REQUIRE(!p.use_vd || d, "nr_mlp_forward_frozen: use_view_dirs needs d (model.py:187-191)");
+    NR_REQUIRE((reinterpret_cast<uintptr_t>(saved_frozen) & 15) == 0,
+               "nr_mlp_forward_frozen: saved_frozen must be 16-byte aligned");
+    NR_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "nr_mlp_forward_frozen: packed must be 16-byte aligned");
+    if (M == 0) return NR_OK;
+    // fp32: the training forward (its backward reads the activations)
+    if (p.prec == NR_PREC_FP32) return nr_mlp_forward(cfg, packed, params, x, d, M, rgb, sigma, saved_frozen, stream);
+    const FrozenSizes f = make_frozen_sizes(p, M);
+    const RbmArgs r = rbm_args(p, packed, params, x, d, M, f.tiles, rgb, sigma, saved_frozen);  // mask_off = 0
+    return launch_fwd_rbm_masks(p, r, static_cast<hipStream_t>(stream));
+}
+
+int nr_mlp_backward_input(const NrMlpConfig* cfg, const void* packed, const float* params, const float* x,
+                          const float* d, int64_t M, const float* rgb, const float* sigma, const void* saved_frozen,
+                          const float* g_rgb, const float* g_sigma, float* g_x, float* g_d, void* workspace,
+                          nr_stream_t stream) {
+    MlpPlan p;
+    if (!plan_or_error(cfg, &p)) return NR_EARG;
+    NR_REQUIRE(packed && params && x && rgb && sigma && saved_frozen && g_rgb && g_sigma && workspace && M >= 0,
+               "nr_mlp_backward_input: null pointer");
+    NR_REQUIRE(!g_d || (d && p.use_vd), "nr_mlp_backward_input: g_d needs d and use_view_dirs");
+    NR_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(saved_frozen)) & 15) == 0,
+               "nr_mlp_backward_input: saved_frozen and workspace must be 16-byte aligned");
+    if (M == 0 || !(g_x || g_d)) return NR_OK;
+    // fp32: the dx stage of the training backward, which computes g_x / g_d itself
+    if (p.prec == NR_PREC_FP32)
+        return nr_mlp_backward_dx(cfg, packed, params, x, d, M, rgb, sigma, saved_frozen, g_rgb, g_sigma, g_x, g_d,
+                                  workspace, stream);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const FrozenSizes f = make_frozen_sizes(p, M);
+    NR_REQUIRE(f.tiles + kScratchTiles < (int64_t{1} << 32), "nr_mlp_backward_input: M beyond 2^37 samples");
+    char* wsb = static_cast<char*>(workspace);
+    uint8_t* tflags = reinterpret_cast<uint8_t*>(wsb + f.flags_off);
+    uint32_t* blkcnt = reinterpret_cast<uint32_t*>(wsb + f.blkcnt_off);
+    if (const int rc = launch_tile_flags(g_rgb, g_sigma, M, p.dense_bwd, f.nseg, tflags, blkcnt, s)) return rc;
+    BwdrArgs r = bwdr_args(p, packed, M, f.tiles, f.nseg, rgb, sigma, saved_frozen, g_rgb, g_sigma, wsb, tflags, blkcnt);
+    r.scratch_base = f.scratch_base;  // mask_off = 0; no dW list
+    r.keep_dz = f.keep_dz;
+    // the offsets mlp_dinput_kernel reads, in the training structs' terms
+    MlpSizes z;
+    std::memset(&z, 0, sizeof(z));
+    z.tiles = f.tiles;
+    z.flags_off = f.flags_off;
+    for (int l = 0; l < p.n_layers; ++l) z.ws_off[WS_DZ0 + l] = r.ws_off[WS_DZ0 + l] = f.dz_off[l];
+    z.ws_off[p.ws_dir] = r.ws_off[p.ws_dir] = f.dz_dir_off;
+    if (const int rc = launch_bwd_rbm_input(p, r, s)) return rc;
+    return input_grads16(p, z, r.packed, x, d, g_x, g_d, wsb, M, s);
 }
 
 int64_t nr_mlp_active_tiles_offset(const NrMlpConfig* cfg, int64_t M) {

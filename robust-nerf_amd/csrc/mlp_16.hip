@@ -174,7 +174,7 @@ __global__ __launch_bounds__(kDinNT) void mlp_dinput_kernel(DinArgs a) {
 
 namespace {
 
-template <int PREC, bool TRAIN>
+template <int PREC, bool TRAIN, bool ACT = TRAIN>
 int launch_fwd_rbm_t(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
     // every chunk fits a slot (checked at compile time per layer shape).  Eight waves per
     // workgroup at every size: four- and six-wave workgroups for small launches (all CUs
@@ -186,7 +186,7 @@ int launch_fwd_rbm_t(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
     const size_t lds = rbm_lds_bytes(p.XB, W);
 #define NR_FWDR(XB_, DB_)                                                                           \
     if (p.XB == XB_ && p.DB == DB_) {                                                               \
-        hipLaunchKernelGGL((mlp_fwd_rbm_kernel<PREC, XB_, DB_, TRAIN, W>), grid, block, lds, s, a); \
+        hipLaunchKernelGGL((mlp_fwd_rbm_kernel<PREC, XB_, DB_, TRAIN, W, ACT>), grid, block, lds, s, a); \
         return check_launch("nr_mlp_forward");                                                      \
     }
     NR_FWDR(2, 1)
@@ -200,7 +200,7 @@ int launch_fwd_rbm_t(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
     return NR_EARG;
 }
 
-template <int PREC>
+template <int PREC, bool INPUT = false>
 int launch_bwd_rbm_t(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
     constexpr int W = kRbmWaves;
     const size_t lds = bwdr_lds_bytes(p.n_mask, W);
@@ -210,8 +210,8 @@ int launch_bwd_rbm_t(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
     }
     // every part of every segment (mlp_bwd_rbm_kernel's workgroup mapping)
     const dim3 grid(static_cast<unsigned>(a.nseg * (kSegTiles / W))), block(W * 64);
-    hipLaunchKernelGGL((mlp_bwd_rbm_kernel<PREC, W>), grid, block, lds, s, a);
-    return check_launch("nr_mlp_backward_dx");
+    hipLaunchKernelGGL((mlp_bwd_rbm_kernel<PREC, W, INPUT>), grid, block, lds, s, a);
+    return check_launch(INPUT ? "nr_mlp_backward_input" : "nr_mlp_backward_dx");
 }
 
 template <int PREC>
@@ -250,6 +250,16 @@ int launch_fwd_rbm(const MlpPlan& p, const RbmArgs& a, bool train, hipStream_t s
 
 int launch_bwd_rbm(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
     return p.prec == NR_PREC_BF16 ? launch_bwd_rbm_t<NR_PREC_BF16>(p, a, s) : launch_bwd_rbm_t<NR_PREC_FP16>(p, a, s);
+}
+
+int launch_fwd_rbm_masks(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
+    return p.prec == NR_PREC_BF16 ? launch_fwd_rbm_t<NR_PREC_BF16, true, false>(p, a, s)
+                                  : launch_fwd_rbm_t<NR_PREC_FP16, true, false>(p, a, s);
+}
+
+int launch_bwd_rbm_input(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
+    return p.prec == NR_PREC_BF16 ? launch_bwd_rbm_t<NR_PREC_BF16, true>(p, a, s)
+                                  : launch_bwd_rbm_t<NR_PREC_FP16, true>(p, a, s);
 }
 
 // 16-bit g_x / g_d: one MFMA pass over the stored dz images of the x_enc-reading

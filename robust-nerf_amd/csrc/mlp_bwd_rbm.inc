@@ -25,7 +25,8 @@ __host__ __device__ constexpr int bwdr_sig_off(int n_mask, int W) { return 2 * k
 __host__ __device__ constexpr int bwdr_lds_bytes(int n_mask, int W) { return bwdr_sig_off(n_mask, W) + 1024; }
 
 // dz of a layer's hidden input: ReLU mask of the forward activation, pack, store
-template <int PREC>
+// (OPT: the input-only chain stores the image only when `keep`, and counts only then)
+template <int PREC, bool OPT = false>
 struct BwdrTrunkFin {
     InBlk<PREC> (&out)[kHB];
     u32x4 mw;
@@ -35,6 +36,7 @@ struct BwdrTrunkFin {
     bool sig;            // feature layer: + w_sigma dz_sigma first
     float dzs;
     const float* wsig;   // LDS: w_sigma vector image, this lane's half
+    bool keep = true;
     __device__ __forceinline__ void operator()(int rb, f32x16& a, const bf16x8&) const {
         if (sig)
 #pragma unroll
@@ -44,13 +46,15 @@ struct BwdrTrunkFin {
                 for (int e = 0; e < 4; ++e) a[4 * g + e] = fmaf(w[e], dzs, a[4 * g + e]);
             }
         to_in_masked<PREC>(a, mw, rb, out[rb]);
-        store_img<PREC>(dst, tile, kHB, rb, out[rb], 0);
-        nvm += 2;
+        if (!OPT || keep) {  // workgroup-uniform
+            store_img<PREC>(dst, tile, kHB, rb, out[rb], 0);
+            nvm += 2;
+        }
     }
 };
 
 // dz_feat = d feat (feature_linear has no activation)
-template <int PREC>
+template <int PREC, bool STORE = true>
 struct BwdrFeatFin {
     InBlk<PREC> (&out)[kHB];
     char* dst;
@@ -58,12 +62,20 @@ struct BwdrFeatFin {
     int& nvm;
     __device__ __forceinline__ void operator()(int rb, f32x16& a, const bf16x8&) const {
         to_in<PREC>(a, out[rb]);
-        store_img<PREC>(dst, tile, kHB, rb, out[rb], 0);
-        nvm += 2;
+        if constexpr (STORE) {
+            store_img<PREC>(dst, tile, kHB, rb, out[rb], 0);
+            nvm += 2;
+        }
     }
 };
 
-template <int PREC, int W>
+// INPUT: the input-only chain of a frozen field (nr_mlp_backward_input).  It stores only the
+// dz images mlp_dinput_kernel reads (dz_c and the trunk layers of a.keep_dz), into the
+// compact workspace of FrozenSizes, builds no dW list, and reads its masks from a region
+// without scratch tiles (a wave without a tile takes tile 0's: its inputs are zero and
+// its stores land in its scratch tile).  s.nvm counts the stores actually issued; which
+// layers store is the same for every wave of the launch.
+template <int PREC, int W, bool INPUT = false>
 __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
     static_assert(kSegTiles % W == 0, "whole parts per segment");
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -77,7 +89,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
     // barriers need every wave anyway)
     const TileSel ts = select_tile(a.flags, a.blk_count, a.nseg, a.tiles, W, wv);
     if (ts.idle) {  // workgroup-uniform
-        finish_tiles(ts, a.nseg, a.tiles, a.dw_list, a.count);
+        if constexpr (!INPUT) finish_tiles(ts, a.nseg, a.tiles, a.dw_list, a.count);
         return;
     }
     const int64_t tile = ts.live ? ts.tile : a.scratch_base + ((blockIdx.x * W + wv) & (kScratchTiles - 1));
@@ -90,7 +102,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
     // stream's first chunk, so its boundary wait publishes them.  The dir layer's
     // mask (needed before the stream) is also read directly.
     char* mlds = lds + bwdr_mask_off() + wv * a.n_mask * 1024;
-    const char* msrc = a.saved + a.mask_off + tile * a.n_mask * 1024;
+    const char* msrc = a.saved + a.mask_off + (INPUT && !ts.live ? 0 : tile) * a.n_mask * 1024;
     for (int l = 0; l < a.n_mask; ++l)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(msrc + l * 1024 + lane16()),
                                          (__attribute__((address_space(3))) void*)(mlds + l * 1024), 16, 0, 0);
@@ -118,7 +130,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
         }
         dzs = (a.sigma[m] > 0.f ? a.g_sigma[m] : 0.f) * a.gscale;
     }
-    {
+    if constexpr (!INPUT) {
         // dz of the heads as one 32-feature block: feature 0 sigma, 1..3 rgb
         f32x16 hb;
         zero(hb);
@@ -157,19 +169,21 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
     InBlk<PREC> hA[kHB], hB[kHB];
     // dz_feat = W_dir[:, feat]^T dz_c
     {
-        BwdrFeatFin<PREC> fin{hA, a.ws + a.ws_off[a.ws_feat], tile, s.nvm};
+        BwdrFeatFin<PREC, !INPUT> fin{hA, a.ws + a.ws_off[a.ws_feat], tile, s.nvm};
         auto in = [&](int kb) -> const InBlk<PREC>& { return cin[kb]; };
         rbm_layer<PREC, NC, kHB, 0, decltype(in), decltype(fin), 0>(s, CK_H, in, fin);
     }
     // dz_{n-1} = (W_feat^T dz_feat + w_sigma dz_sigma) * [h_{n-1} > 0]
     {
-        BwdrTrunkFin<PREC> fin{hB, mask_of(n - 1), a.ws + a.ws_off[WS_DZ0 + n - 1], tile, s.nvm, true, dzs, wsig};
+        BwdrTrunkFin<PREC, INPUT> fin{hB, mask_of(n - 1), a.ws + a.ws_off[WS_DZ0 + n - 1], tile, s.nvm, true, dzs,
+                                      wsig, !INPUT || ((a.keep_dz >> (n - 1)) & 1u)};
         auto in = [&](int kb) -> const InBlk<PREC>& { return hA[kb]; };
         rbm_layer<PREC, kHB, kHB, 0, decltype(in), decltype(fin), 0>(s, n > 1 ? CK_H : 0, in, fin);
     }
     // dz_{i-1} = (W_i[:, h]^T dz_i) * [h_{i-1} > 0]
     auto trunk = [&](int i, InBlk<PREC>(&hin)[kHB], InBlk<PREC>(&hout)[kHB]) {
-        BwdrTrunkFin<PREC> fin{hout, mask_of(i - 1), a.ws + a.ws_off[WS_DZ0 + i - 1], tile, s.nvm, false, 0.f, wsig};
+        BwdrTrunkFin<PREC, INPUT> fin{hout, mask_of(i - 1), a.ws + a.ws_off[WS_DZ0 + i - 1], tile, s.nvm, false, 0.f,
+                                      wsig, !INPUT || ((a.keep_dz >> (i - 1)) & 1u)};
         auto in = [&](int kb) -> const InBlk<PREC>& { return hin[kb]; };
         rbm_layer<PREC, kHB, kHB, 0, decltype(in), decltype(fin), 0>(s, i > 1 ? CK_H : 0, in, fin);
     };
@@ -178,5 +192,5 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
         if (i == 1) break;
         trunk(i - 1, hA, hB);
     }
-    finish_tiles(ts, a.nseg, a.tiles, a.dw_list, a.count);
+    if constexpr (!INPUT) finish_tiles(ts, a.nseg, a.tiles, a.dw_list, a.count);
 }

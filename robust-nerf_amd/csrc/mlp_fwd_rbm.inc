@@ -169,7 +169,7 @@ __device__ __forceinline__ void rbm_layer(RStream& s, int next_ckb, const In& in
 // ---- row-block epilogues ----
 // trunk layer: bias, 16-bit pack, ReLU on packed pairs, mask bits; training stores the
 // block (B-operand image of h_i); the last trunk layer also feeds the sigma head
-template <int PREC, bool TRAIN>
+template <int PREC, bool TRAIN, bool ACT = TRAIN>
 struct RbmTrunkFin {
     InBlk<PREC> (&out)[kHB];
     unsigned (&mw)[4];
@@ -184,7 +184,7 @@ struct RbmTrunkFin {
         bf16x8 o[2];
         epi16_blk<PREC, true, TRAIN>(a, o, mw, rb);
         out[rb] = InBlk<PREC>{{o[0], o[1]}};
-        if constexpr (TRAIN) {
+        if constexpr (ACT) {
             store_img<PREC>(sv, tile, kHB, rb, out[rb], 0);
             nvm += 2;
         }
@@ -200,7 +200,7 @@ struct RbmTrunkFin {
 };
 
 // feature_linear: bias, 16-bit pack (no activation); training stores feat
-template <int PREC, bool TRAIN>
+template <int PREC, bool ACT>
 struct RbmFeatFin {
     InBlk<PREC> (&out)[kHB];
     char* sv;
@@ -212,7 +212,7 @@ struct RbmFeatFin {
         unsigned unused[4];
         epi16_blk<PREC, false, false>(a, o, unused, rb);
         out[rb] = InBlk<PREC>{{o[0], o[1]}};
-        if constexpr (TRAIN) {
+        if constexpr (ACT) {
             store_img<PREC>(sv, tile, kHB, rb, out[rb], 0);
             nvm += 2;
         }
@@ -221,7 +221,7 @@ struct RbmFeatFin {
 
 // dir_linear: bias, ReLU in fp32 (the rgb head reads it), pack + mask bits; training
 // stores h_c; the three rgb rows accumulate
-template <int PREC, bool TRAIN>
+template <int PREC, bool TRAIN, bool ACT = TRAIN>
 struct RbmDirFin {
     unsigned (&mw)[4];
     char* sv;
@@ -236,7 +236,7 @@ struct RbmDirFin {
         for (int r = 0; r < 16; ++r) a[r] = relu_f(a[r]);
         bf16x8 o[2];
         epi16_blk<PREC, false, TRAIN>(a, o, mw, rb);
-        if constexpr (TRAIN) {
+        if constexpr (ACT) {
             store_img<PREC>(sv, tile, NC, rb, InBlk<PREC>{{o[0], o[1]}}, 0);
             nvm += 2;
         }
@@ -262,9 +262,15 @@ __device__ __forceinline__ void rbm_xenc(const PeRev& pr, int L, bool h1, InBlk<
     }
 }
 
-template <int PREC, int XB, int DB, bool TRAIN, int W>
+// TRAIN: the ReLU masks are built and stored; ACT: so are the activation images (x_enc,
+// h_i, feat, d_enc, h_c).  <true, true> is the training forward, <false, false> inference,
+// <true, false> the frozen-field forward: masks alone, into a region without padding
+// tiles, so a wave past the last tile stores nothing and counts nothing into s.nvm (the
+// count is per wave, and so is each stream wait).
+template <int PREC, int XB, int DB, bool TRAIN, int W, bool ACT = TRAIN>
 __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
     static_assert(W >= 3, "waves 0..2 stage the head weights");
+    static_assert(TRAIN || !ACT, "activation images come with the masks");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, ml = lane & 31;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -295,7 +301,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
     for (int kb = 0; kb < XB; ++kb) {
         *reinterpret_cast<bf16x8*>(xlds + (2 * kb) * kFragBytes + lane16()) = xe[kb].s[0];
         *reinterpret_cast<bf16x8*>(xlds + (2 * kb + 1) * kFragBytes + lane16()) = xe[kb].s[1];
-        if constexpr (TRAIN) store_img<PREC>(a.saved + a.sv_off[SV_XENC], tile, XB, kb, xe[kb], 0);
+        if constexpr (ACT) store_img<PREC>(a.saved + a.sv_off[SV_XENC], tile, XB, kb, xe[kb], 0);
     }
 
     RStream s{lds, a.packed + a.base, -1, 0, wv, kRbmSlot, W};
@@ -316,12 +322,14 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
         constexpr int KBL = decltype(kbc)::value, XL = decltype(xlc)::value;
 #pragma unroll
         for (int q = 0; q < 4; ++q) mw[q] = 0u;
-        RbmTrunkFin<PREC, TRAIN> fin{hout, mw, TRAIN ? a.saved + a.sv_off[SV_H0 + i] : nullptr, tile, s.nvm,
-                                     i == n - 1, sg, hl};
+        RbmTrunkFin<PREC, TRAIN, ACT> fin{hout, mw, ACT ? a.saved + a.sv_off[SV_H0 + i] : nullptr, tile, s.nvm,
+                                          i == n - 1, sg, hl};
         rbm_layer<PREC, KBL, kHB, XL>(s, ckb_of(i + 1), in, fin, xaddr);
         if constexpr (TRAIN) {
-            masks[(tile * a.n_mask + i) * 64 + lane] = u32x4{mw[0], mw[1], mw[2], mw[3]};
-            s.nvm += 1;
+            if (ACT || tile < a.tiles) {  // wave-uniform
+                masks[(tile * a.n_mask + i) * 64 + lane] = u32x4{mw[0], mw[1], mw[2], mw[3]};
+                s.nvm += 1;
+            }
         }
     };
     // trunk layer i (i >= 1) from hin into hout: plain, or [x_enc, h] after a skip
@@ -356,7 +364,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
 
     // feature_linear: h_{n-1} (hA) -> feat (hB)
     {
-        RbmFeatFin<PREC, TRAIN> fin{hB, TRAIN ? a.saved + a.sv_off[a.sv_feat] : nullptr, tile, s.nvm};
+        RbmFeatFin<PREC, ACT> fin{hB, ACT ? a.saved + a.sv_off[a.sv_feat] : nullptr, tile, s.nvm};
         auto in = [&](int kb) -> const InBlk<PREC>& { return hA[kb]; };
         rbm_layer<PREC, kHB, kHB, 0>(s, rbm_chunk_kb(kHB + DB), in, fin);
     }
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
             for (int r = 0; r < 16; ++r)
                 v[r] = pe_fast(pr, 32 * kb + acc_row(r, 0), 32 * kb + acc_row(r, 1), h != 0, a.Ld);
             to_in<PREC>(v, de[kb]);
-            if constexpr (TRAIN) {
+            if constexpr (ACT) {
                 store_img<PREC>(a.saved + a.sv_off[a.sv_denc], tile, DB, kb, de[kb], 0);
                 s.nvm += 2;
             }
@@ -381,10 +389,11 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
     {
 #pragma unroll
         for (int q = 0; q < 4; ++q) mw[q] = 0u;
-        RbmDirFin<PREC, TRAIN> fin{mw, TRAIN ? a.saved + a.sv_off[a.sv_hc] : nullptr, tile, s.nvm, sc, hl + 256};
+        RbmDirFin<PREC, TRAIN, ACT> fin{mw, ACT ? a.saved + a.sv_off[a.sv_hc] : nullptr, tile, s.nvm, sc, hl + 256};
         auto in = [&](int kb) -> const InBlk<PREC>& { return kb < kHB ? hB[kb] : de[kb >= kHB ? kb - kHB : 0]; };
         rbm_layer<PREC, kHB + DB, kHB / 2, 0>(s, 0, in, fin);
-        if constexpr (TRAIN) masks[(tile * a.n_mask + n) * 64 + lane] = u32x4{mw[0], mw[1], mw[2], mw[3]};
+        if constexpr (TRAIN)
+            if (ACT || tile < a.tiles) masks[(tile * a.n_mask + n) * 64 + lane] = u32x4{mw[0], mw[1], mw[2], mw[3]};
     }
 
     // heads: sigma = relu(w_sigma . h_{n-1} + b), rgb = sigmoid(W_rgb h_c + b)

@@ -126,10 +126,16 @@ struct BwdrArgs {
     int n_mask;
     int64_t ws_off[kMaxTrunk + 3];
     int ws_feat, ws_dir, ws_heads;
+    uint32_t keep_dz;    // input-only chain: bit l set <=> trunk layer l's dz image is stored
 };
 
 int launch_fwd_rbm(const MlpPlan& p, const RbmArgs& a, bool train, hipStream_t s);
 int launch_bwd_rbm(const MlpPlan& p, const BwdrArgs& a, hipStream_t s);
+// frozen field (FrozenSizes, mlp_plan.hpp): the forward that stores the ReLU masks alone
+// (a.saved = the mask region, a.mask_off = 0), and the dX chain that stores only the dz
+// images of a.keep_dz and dz_c and builds no dW list
+int launch_fwd_rbm_masks(const MlpPlan& p, const RbmArgs& a, hipStream_t s);
+int launch_bwd_rbm_input(const MlpPlan& p, const BwdrArgs& a, hipStream_t s);
 // g_x / g_d from the dz images the dX chain stored (mlp_dinput_kernel)
 int input_grads16(const MlpPlan& p, const MlpSizes& z, const char* packed, const float* x, const float* d, float* g_x,
                   float* g_d, const char* ws, int64_t M, hipStream_t s);

@@ -406,4 +406,36 @@ MlpSizes make_sizes(const MlpPlan& p, int64_t M) {
     return s;
 }
 
+FrozenSizes make_frozen_sizes(const MlpPlan& p, int64_t M) {
+    FrozenSizes f;
+    std::memset(&f, 0, sizeof(f));
+    const MlpSizes t = make_sizes(p, M);
+    f.tiles = t.tiles;
+    f.nseg = t.nseg;
+    if (p.fpb != 2) {
+        // fp32: the training buffers (the chunk-major backward reads the activations)
+        f.saved_bytes = t.saved_bytes;
+        f.ws_bytes = t.ws_bytes;
+        return f;
+    }
+    f.saved_bytes = f.tiles * p.n_mask * kFragBytes;
+    f.scratch_base = f.tiles;
+    const int64_t img_tiles = f.tiles + kScratchTiles;
+    int64_t off = 0;
+    for (int l = 0; l < p.n_layers; ++l) {
+        if (l > 0 && !is_skip(p, l - 1)) continue;
+        f.keep_dz |= 1u << l;
+        f.dz_off[l] = off;
+        off = align256(off + img_tiles * kHidden * 32 * p.esize);
+    }
+    f.dz_dir_off = off;
+    off = align256(off + img_tiles * (kHidden / 2) * 32 * p.esize);
+    f.flags_off = off;
+    off = align256(off + f.nseg * kSegTiles);
+    f.blkcnt_off = off;
+    off = align256(off + f.nseg * (kSegTiles / 64) * 4);
+    f.ws_bytes = off;
+    return f;
+}
+
 }  // namespace nr

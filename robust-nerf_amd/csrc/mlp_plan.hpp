@@ -157,4 +157,35 @@ struct MlpSizes {
 
 MlpSizes make_sizes(const MlpPlan& p, int64_t M);
 
+// Frozen field (nr_mlp_forward_frozen / nr_mlp_backward_input): what a backward that
+// produces g_x / g_d alone reads, and nothing else.
+//
+// 16-bit.  saved_frozen is the ReLU mask region by itself: tiles * n_mask KB, tile-major
+// ([tile][mask word][64 lanes x 16 B], as the training layout's mask region, at offset
+// 0), with no padding tiles: forward waves past the last tile store nothing, and dX waves
+// without a tile read tile 0's masks (their inputs are zero).  The workspace, in order,
+// every part 256-byte aligned:
+//   dz image of each x_enc-reading trunk layer (layer 0 and every layer after a skip), in
+//     layer order: (tiles + kScratchTiles) tiles x kHB blocks x 2 KB
+//   dz_c image: (tiles + kScratchTiles) tiles x kHB/2 blocks x 2 KB
+//   tile flags: nseg * kSegTiles bytes
+//   64-tile block counts: nseg * (kSegTiles / 64) uint32
+// The scratch tiles (dX waves without an active tile store there) are tiles
+// [tiles, tiles + kScratchTiles) of every image.  No dz_heads, dz_feat or other trunk
+// dz, no dW list, count or slabs.
+//
+// fp32 (parity mode): the chunk-major backward reads the saved activations, so both
+// buffers have the training layout and sizes (make_sizes).
+struct FrozenSizes {
+    int64_t tiles, nseg;
+    int64_t saved_bytes;               // mask_off is 0
+    uint32_t keep_dz;                  // bit l: trunk layer l's dz image is in the workspace
+    int64_t dz_off[kMaxTrunk];         // bytes, valid for the layers of keep_dz
+    int64_t dz_dir_off, flags_off, blkcnt_off;
+    int64_t scratch_base;              // first scratch tile of the images
+    int64_t ws_bytes;
+};
+
+FrozenSizes make_frozen_sizes(const MlpPlan& p, int64_t M);
+
 }  // namespace nr

@@ -107,6 +107,11 @@ _SIGNATURES = {
     "nr_mlp_backward_dw": (c_i, [_cfg_p, c_i64, c_vp, c_vp, c_vp]),
     "nr_mlp_backward_reduce": (c_i, [_cfg_p, c_i64, c_vp, c_vp, c_vp]),
     "nr_mlp_active_tiles_offset": (c_i64, [_cfg_p, c_i64]),
+    "nr_mlp_frozen_saved_bytes": (c_i64, [_cfg_p, c_i64]),
+    "nr_mlp_frozen_workspace_bytes": (c_i64, [_cfg_p, c_i64]),
+    "nr_mlp_forward_frozen": (c_i, [_cfg_p, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "nr_mlp_backward_input": (c_i, [_cfg_p, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp]),
     "nr_sumsq_workspace_bytes": (c_i64, []),
     "nr_sumsq": (c_i, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "nr_adam_step": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_d, c_d, c_d, c_d, c_i64, c_vp, c_f, c_vp]),

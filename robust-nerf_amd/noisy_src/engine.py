@@ -554,6 +554,71 @@ class PoseTrainer:
         return metrics
 
 
+class PoseRefiner:
+    """Photometric pose refinement against a FROZEN field: the pose half of
+    ``PoseTrainer.step`` and nothing else (BARF's test-time protocol).  Poses from the
+    SE(3) kernel, the batch's rays from them, render coarse+fine with the MSE losses
+    (``loss_coarse + loss_fine``), backward, one fused pose Adam with the 0.1 clip.  No
+    regulariser, no network optimizer, no host synchronisation (losses stay on the device).
+
+    Both networks' parameters are set to ``requires_grad_(False)`` for the refiner's
+    lifetime, so the fused MLP takes its input-gradient-only path (masks-only forward,
+    no dW); ``close()`` or leaving the ``with`` block restores them.  ``camera_params``
+    must use the small-angle Jacobian (``fixed_small_angle=True``): refinement starts at
+    w = 0, where the reference's ``theta < 1e-6`` rule gives a rotation gradient of
+    exactly zero.  ``lr_decay`` (optional): the LambdaLR of the training loops."""
+
+    def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,
+                 pose_lr: float = 1e-3, max_norm: float = 0.1, lr_decay: Optional[int] = None):
+        if camera_params.learn_rotation and not camera_params.fixed_small_angle:
+            raise ValueError("PoseRefiner needs CameraPoseParameters(fixed_small_angle=True): at w = 0 the "
+                             "reference's theta < 1e-6 rule blocks the rotation gradient, so the poses could not turn")
+        self.poses = list(camera_params.parameters())
+        if not self.poses:
+            raise ValueError("PoseRefiner: camera_params has no learnable rotation or translation")
+        self.model_coarse, self.model_fine = model_coarse, model_fine
+        self.camera_params, self.pixel_sampler, self.render_config = camera_params, pixel_sampler, render_config
+        self.max_norm = max_norm
+        self._frozen = [(p, p.requires_grad) for net in (model_coarse, model_fine) if net is not None
+                        for p in net.parameters()]
+        for p, _ in self._frozen:
+            p.requires_grad_(False)
+        self.optimizer_poses = FusedAdam(self.poses, lr=pose_lr)
+        self.scheduler_poses = (torch.optim.lr_scheduler.LambdaLR(self.optimizer_poses, lr_lambda_factory(lr_decay))
+                                if lr_decay is not None else None)
+
+    def close(self) -> None:
+        """Give the networks' parameters their ``requires_grad`` back."""
+        for p, was in self._frozen:
+            p.requires_grad_(was)
+        self._frozen = []
+
+    def __enter__(self) -> "PoseRefiner":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def step(self, pixel_batch, t_rand: Optional[torch.Tensor] = None,
+             u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        self.optimizer_poses.zero_grad(set_to_none=True)
+        poses = self.camera_params.get_all_poses()
+        rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses)
+        out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
+                          t_rand=t_rand, u=u, target_rgb=pixel_batch.target_rgb)
+        loss = out["loss_coarse"]
+        metrics = {"loss_coarse": loss.detach()}
+        if "loss_fine" in out:
+            metrics["loss_fine"] = out["loss_fine"].detach()
+            loss = loss + out["loss_fine"]
+        loss.backward(ops.unit_grad(loss.device))
+        self.optimizer_poses.step(clip_groups=[(self.poses, self.max_norm)])
+        if self.scheduler_poses is not None:
+            self.scheduler_poses.step()
+        metrics["loss"] = loss.detach()
+        return metrics
+
+
 class _AdamSchedule:
     """One FusedAdam's share of a captured step (GraphedTrainer, GraphedPoseTrainer): the
     8-byte device pair its Adam launch reads (``FusedAdam.device_sched``), the pinned

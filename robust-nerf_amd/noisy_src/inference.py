@@ -19,6 +19,13 @@ ckpt.pt --mode test --rotation_noise 1.0``) with a working ``--mode single``,
 entry point runs the fused image tail (``fused_tail=True``): ``metrics.image_metrics``
 (fp64 SSIM, one read-back per image) and the 8-bit frames of ``frame_u8`` /
 ``depth_frame_u8`` written on the device (csrc/image.hip).
+
+Pose-optimised checkpoints (no reference counterpart; BARF's evaluation protocol):
+``--align_train_poses`` carries the ground-truth test poses into the frame the field was
+trained in (``pose_eval.align_sim3`` of the checkpoint's optimised train poses against
+the train split's), and ``--refine_poses ITERS`` refines every test pose photometrically
+against its own image on the frozen field (``engine.PoseRefiner``) before it is rendered
+and scored.  Without either flag the outputs are byte for byte what they were.
 """
 
 from __future__ import annotations
@@ -164,13 +171,14 @@ def create_spiral_poses(n_frames: int = 120, radius: float = 0.5, height: float 
     return torch.from_numpy(c2w).to(device)
 
 
-def _noisy_poses(test_data, noise_config: NoiseConfig):
-    """Every view's (pose, noise info) in view order, as the reference's loop draws them."""
+def _noisy_poses(test_data, noise_config: NoiseConfig, poses: Optional[torch.Tensor] = None):
+    """Every view's (pose, noise info) in view order, as the reference's loop draws them.
+    ``poses``: the clean poses when they are not ``test_data.poses`` (the learned frame)."""
     if noise_config.seed is not None:
         set_noise_seed(noise_config.seed)
     out = []
     for i in range(test_data.images.shape[0]):
-        orig = test_data.poses[i]
+        orig = test_data.poses[i] if poses is None else poses[i]
         if noise_config.has_noise:
             pose, info = add_noise_to_pose(orig, rotation_noise_deg=noise_config.rotation_noise_deg,
                                            translation_noise=noise_config.translation_noise)
@@ -194,32 +202,141 @@ def _rank0_draws(views, noise_config: NoiseConfig, process_group):
     return [(p.to(device), info) for p, info in obj[0]]
 
 
+def checkpoint_train_poses(checkpoint_path: Path) -> torch.Tensor:
+    """The optimised train poses (N,4,4) a ``train_pose_opt`` checkpoint carries
+    (``camera_params``: initial poses and the learned deltas), composed on the host in fp64
+    with the SE(3) map of the training run: R = exp([w]x) R_0, t = t_0 + dt."""
+    ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+    cam = ckpt.get("camera_params")
+    if cam is None or "initial_poses" not in cam:
+        raise SystemExit(f"--align_train_poses: {checkpoint_path} carries no camera_params (it was not written by "
+                         "noisy_src.train_pose_opt), so there are no optimised train poses to align")
+    init = cam["initial_poses"].to(torch.float64)
+    n = init.shape[0]
+    w = cam.get("rotation_deltas", torch.zeros(n, 3)).to(torch.float64)
+    dt = cam.get("translation_deltas", torch.zeros(n, 3)).to(torch.float64)
+    K = torch.zeros(n, 3, 3, dtype=torch.float64)
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0] = -w[:, 2], w[:, 1], w[:, 2]
+    K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -w[:, 0], -w[:, 1], w[:, 0]
+    out = init.clone()
+    out[:, :3, :3] = torch.linalg.matrix_exp(K) @ init[:, :3, :3]
+    out[:, :3, 3] = init[:, :3, 3] + dt
+    return out
+
+
+def refine_view_poses(renderer: NeRFRenderer, test_data, poses: Dict[int, torch.Tensor], iters: int, lr: float = 1e-3,
+                      rays_per_view: int = 256, chunk_size: int = 1024 * 4, seed: int = 0,
+                      log=print) -> Dict[int, torch.Tensor]:
+    """Photometric refinement of test poses on the frozen field: ``poses`` (view -> (4,4))
+    are refined against their own images in groups of ``chunk_size // rays_per_view`` views,
+    ``iters`` steps of ``engine.PoseRefiner`` per group with ``rays_per_view`` random pixels
+    of every view of the group.  Sampling jitter follows the render config; the density
+    noise of training (``raw_noise_std``) is off.  Every draw comes from a generator seeded
+    with ``seed`` and the group's first view, so a view's result does not depend on the
+    groups before it."""
+    import dataclasses
+    from types import SimpleNamespace
+
+    from . import ops
+    from .data_pose_opt import PixelBatch, PixelDataset, PixelSampler
+    from .engine import PoseRefiner
+    from .train_pose_opt import CameraPoseParameters
+
+    if rays_per_view < 1 or rays_per_view > chunk_size:
+        raise ValueError(f"refine_rays_per_view must be in [1, chunk_size = {chunk_size}], got {rays_per_view}")
+    views = sorted(poses)
+    per_group = max(1, chunk_size // rays_per_view)
+    rc = dataclasses.replace(renderer.config, raw_noise_std=0.0)
+    H, W = test_data.H, test_data.W
+    out: Dict[int, torch.Tensor] = {}
+    with torch.enable_grad():
+        for g0 in range(0, len(views), per_group):
+            group = views[g0:g0 + per_group]
+            dev = test_data.images.device
+            init = torch.stack([poses[v].to(dev).float() for v in group])
+            ds = PixelDataset(SimpleNamespace(H=H, W=W, focal=test_data.focal, images=test_data.images[group]))
+            sampler = PixelSampler(ds, batch_size=len(group) * rays_per_view)
+            cam = CameraPoseParameters(init, fixed_small_angle=True).to(dev)
+            gen = torch.Generator(device=dev).manual_seed(int(seed) + int(group[0]))
+            base = (torch.arange(len(group), device=dev) * (H * W)).repeat_interleave(rays_per_view)
+            B = base.numel()
+            first = last = None
+            with PoseRefiner(renderer.model_coarse, renderer.model_fine, cam, sampler, rc, pose_lr=lr) as refiner:
+                for _ in range(iters):
+                    idx = base + torch.randint(0, H * W, (B,), device=dev, generator=gen)
+                    img, pix, rgb = ops.gather_pixels(idx, ds.images, validate=False)
+                    t_rand = torch.rand(B, rc.num_samples, device=dev, generator=gen) if rc.perturb else None
+                    u = torch.rand(B, rc.num_samples_fine, device=dev, generator=gen)
+                    last = refiner.step(PixelBatch(img, pix, rgb, in_range=True), t_rand=t_rand, u=u)["loss"]
+                    first = last if first is None else first
+            with torch.no_grad():
+                refined = cam.get_all_poses()
+            for k, v in enumerate(group):
+                out[v] = refined[k].detach()
+            if first is not None:
+                log(f"  refined views {group[0]}..{group[-1]}: loss {float(first):.5f} -> {float(last):.5f} "
+                    f"({iters} steps of {B} rays)")
+    return out
+
+
 @torch.no_grad()
 def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise_config: NoiseConfig,
                       device: str = "cuda", chunk_size: int = 1024 * 4, process_group=None,
                       save_images: bool = True, log=print, fused_tail: bool = False, *,
-                      view_indices: Optional[Sequence[int]] = None, mode: str = "test") -> Dict[str, object]:
+                      view_indices: Optional[Sequence[int]] = None, mode: str = "test",
+                      refine_iters: int = 0, refine_lr: float = 1e-3, refine_rays_per_view: int = 256,
+                      refine_seed: int = 0, align_train_poses=None) -> Dict[str, object]:
     """Reference inference.py:145-318 (same per-image records, summary keys and files),
     sharded over ``process_group``'s ranks when one is given.  ``fused_tail``: the metrics
     of a view come from ``metrics.image_metrics`` (fp64 SSIM, one read-back) and its PNGs
     from the frame kernels (device only, no CPU fallback).  ``view_indices`` restricts the
     evaluation to those test views (the noise of every view is still drawn, so a view sees
-    the pose it sees in the full run); ``mode`` is recorded in ``experiment_config.json``."""
+    the pose it sees in the full run); ``mode`` is recorded in ``experiment_config.json``.
+
+    ``align_train_poses`` = (optimised train poses, ground-truth train poses): the test
+    poses are carried into the learned frame (``pose_eval``) before the noise is drawn.
+    ``refine_iters`` > 0: each rank then refines the poses of the views it renders
+    (``refine_view_poses``; no collective).  With either, every per-image record gains
+    ``pose_rotation_error_deg_before/after`` and ``pose_translation_error_before/after``
+    (against the ground truth in the frame the view is rendered in) and
+    ``test_metrics.json`` a ``pose_refinement`` block; without, nothing changes."""
     rank, world = 0, 1
     if process_group is not None:
         import torch.distributed as dist
         rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
-    views = _rank0_draws(_noisy_poses(test_data, noise_config), noise_config, process_group)
+    pose_eval_on = refine_iters > 0 or align_train_poses is not None
+    clean, sim3 = None, None
+    if align_train_poses is not None:
+        from .pose_eval import align_sim3, to_learned_frame
+        sim3 = align_sim3(*align_train_poses)
+        clean = to_learned_frame(sim3, test_data.poses).to(test_data.poses.device, torch.float32)
+    views = _rank0_draws(_noisy_poses(test_data, noise_config, clean), noise_config, process_group)
     lpips_metric = LPIPSMetric(device=device)
     order = list(range(test_data.images.shape[0])) if view_indices is None else [int(i) for i in view_indices]
     n_images = len(order)
     if rank == 0:
         log(f"Evaluating {n_images} test images on {world} rank(s)...")
     mine = []
+    refined = {}
+    if refine_iters > 0:
+        refined = refine_view_poses(renderer, test_data, {i: views[i][0] for i in order[rank::world]}, refine_iters,
+                                    lr=refine_lr, rays_per_view=refine_rays_per_view, chunk_size=chunk_size,
+                                    seed=refine_seed, log=log)
     for i in order[rank::world]:
         pose, noise_info = views[i]
+        pose_rec = {}
+        if pose_eval_on:
+            from .pose_eval import pose_error
+            gt = (test_data.poses[i] if clean is None else clean[i]).detach().cpu().double()
+            after = refined.get(i, pose)
+            eb, ea = pose_error(gt, pose.detach().cpu().double()), pose_error(gt, after.detach().cpu().double())
+            pose_rec = {"pose_rotation_error_deg_before": eb["rotation_error_deg"],
+                        "pose_rotation_error_deg_after": ea["rotation_error_deg"],
+                        "pose_translation_error_before": eb["translation_error"],
+                        "pose_translation_error_after": ea["translation_error"]}
+            pose = after
         target = test_data.images[i]
         start = time.time()
         out = render_image(renderer, pose, test_data.H, test_data.W, test_data.focal, chunk_size=chunk_size)
@@ -234,6 +351,7 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
                    "mse": compute_mse(pred, target).item(), "render_time": time.time() - start}
         if noise_info:
             rec.update({f"noise_{k}": v for k, v in noise_info.items()})
+        rec.update(pose_rec)
         lp = lpips_metric(pred, target) if lpips_metric.available else None
         if lp is not None:
             rec["lpips"] = lp.item()
@@ -266,6 +384,14 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
                                "rotation_error_std_deg": float(np.std(rot)),
                                "translation_error_mean": float(np.mean(tr)),
                                "translation_error_std": float(np.std(tr))}
+    if pose_eval_on:
+        avg["pose_refinement"] = {
+            "iters": refine_iters, "lr": refine_lr, "rays_per_view": refine_rays_per_view, "seed": refine_seed,
+            "views_per_group": max(1, chunk_size // max(1, refine_rays_per_view)),
+            "aligned_train_poses": sim3 is not None, "sim3": sim3.to_json() if sim3 is not None else None,
+            **{f"{k}_mean": float(np.mean([r[k] for r in per_image])) for k in (
+                "pose_rotation_error_deg_before", "pose_rotation_error_deg_after",
+                "pose_translation_error_before", "pose_translation_error_after")}}
     if rank == 0:
         (output_dir / "per_image_metrics.json").write_text(json.dumps(per_image, indent=2))
         (output_dir / "test_metrics.json").write_text(json.dumps(avg, indent=2))
@@ -378,6 +504,16 @@ def build_arg_parser():
     video = ap.add_argument_group("Video Options")
     video.add_argument("--n_frames", type=int, default=120, help="Number of frames for video")
     video.add_argument("--fps", type=int, default=30, help="Video FPS")
+    pose = ap.add_argument_group("Pose Evaluation Options (pose-optimised checkpoints; --mode test / single)")
+    pose.add_argument("--align_train_poses", action="store_true",
+                      help="Carry the test poses into the learned frame: Sim(3) alignment of the checkpoint's "
+                           "optimised train poses with the train split's ground truth")
+    pose.add_argument("--refine_poses", type=int, default=0, metavar="ITERS",
+                      help="Photometric test-time refinement steps per group of views on the frozen field (0 = off)")
+    pose.add_argument("--refine_lr", type=float, default=1e-3, help="Pose learning rate of the refinement")
+    pose.add_argument("--refine_rays_per_view", type=int, default=256,
+                      help="Random pixels per view and step (views are grouped chunk_size // this at a time)")
+    pose.add_argument("--refine_seed", type=int, default=0, help="Seed of the refinement's pixel and sample draws")
     perf = ap.add_argument_group("Performance Options")
     perf.add_argument("--chunk_size", type=int, default=1024 * 4, help="Rays per chunk (default: 4096)")
     return ap
@@ -431,8 +567,19 @@ def main(argv=None) -> None:
             else:
                 log("  Mode: Clean (no noise)")
             log(f"{bar}\n")
+            align = None
+            if a.align_train_poses:
+                train_data = load_blender_data(data_root, scene, "train", img_scale, device)
+                align = (checkpoint_train_poses(a.checkpoint), train_data.poses)
+                log("  Test poses carried into the learned frame (Sim(3) alignment of the train poses)")
+            if a.refine_poses > 0:
+                log(f"  Test-time pose refinement: {a.refine_poses} steps, lr {a.refine_lr}, "
+                    f"{a.refine_rays_per_view} rays per view")
             m = evaluate_test_set(renderer, test_data, output_dir, noise_config, device, a.chunk_size,
-                                  process_group=pg, log=log, fused_tail=fused, view_indices=only, mode=a.mode)
+                                  process_group=pg, log=log, fused_tail=fused, view_indices=only, mode=a.mode,
+                                  refine_iters=a.refine_poses, refine_lr=a.refine_lr,
+                                  refine_rays_per_view=a.refine_rays_per_view, refine_seed=a.refine_seed,
+                                  align_train_poses=align)
             log(f"\n{bar}\nTest Set Results:")
             log(f"  PSNR:  {m['psnr_mean']:.2f} ± {m['psnr_std']:.2f} dB")
             log(f"  SSIM:  {m['ssim_mean']:.4f} ± {m['ssim_std']:.4f}")
@@ -443,6 +590,13 @@ def main(argv=None) -> None:
                 log("\nActual Noise Applied:")
                 log(f"  Rotation error:    {act['rotation_error_mean_deg']:.3f} ± {act['rotation_error_std_deg']:.3f}°")
                 log(f"  Translation error: {act['translation_error_mean']:.4f} ± {act['translation_error_std']:.4f}")
+            if "pose_refinement" in m:
+                pr = m["pose_refinement"]
+                log("\nTest poses (before -> after refinement):")
+                log(f"  Rotation error:    {pr['pose_rotation_error_deg_before_mean']:.3f} -> "
+                    f"{pr['pose_rotation_error_deg_after_mean']:.3f}°")
+                log(f"  Translation error: {pr['pose_translation_error_before_mean']:.4f} -> "
+                    f"{pr['pose_translation_error_after_mean']:.4f}")
             log(f"{bar}\nResults saved to: {output_dir}")
         else:
             log("\nLoading data for camera parameters...")
@@ -462,7 +616,7 @@ def main(argv=None) -> None:
 
 __all__ = ["load_checkpoint", "render_image", "save_image", "depth_to_colormap", "frame_u8", "depth_frame_u8",
            "save_frame_u8", "generate_output_folder_name", "create_spiral_poses", "evaluate_test_set", "render_video",
-           "main"]
+           "checkpoint_train_poses", "refine_view_poses", "main"]
 
 if __name__ == "__main__":
     main()

@@ -155,6 +155,10 @@ class _PEWindow:
 # reference form, for A/B runs); by default tiles whose incoming gradient is exactly
 # zero are skipped (csrc/mlp.hip, tile_flags_kernel: identical gradients)
 _DENSE_BACKWARD = os.environ.get("NR_MLP_DENSE_BACKWARD", "0") not in ("", "0")
+# NR_MLP_FROZEN=0 sends a network whose parameters need no gradient (a pose step on a
+# frozen field) through the training kernels, dW included (for A/B runs); by default it
+# takes nr_mlp_forward_frozen / nr_mlp_backward_input (identical input gradients)
+_FROZEN = os.environ.get("NR_MLP_FROZEN", "1") not in ("", "0")
 
 
 def _precision_code(p: str) -> int:
@@ -181,6 +185,8 @@ class _MLPFunction(torch.autograd.Function):
         rgb = torch.empty(M, 3, device=xc.device, dtype=torch.float32)
         sigma = torch.empty(M, 1, device=xc.device, dtype=torch.float32)
         training = any(ctx.needs_input_grad)
+        # x or d needs a gradient and no parameter does: masks-only forward, input-only backward
+        frozen = _FROZEN and training and not any(ctx.needs_input_grad[3:])
         w_pos, w_dir = net._pe_window.device_weights(xc.device)
         if w_pos is not None or w_dir is not None:
             # coarse-to-fine window: folded into the images' encoding columns.  A training
@@ -193,12 +199,14 @@ class _MLPFunction(torch.autograd.Function):
                 net._fold_key = fold_key
         saved = None
         if training and M > 0:
-            saved = torch.empty(int(_hip.load().nr_mlp_saved_bytes(cfg, M)), device=xc.device, dtype=torch.uint8)
-        call("nr_mlp_forward", cfg, ptr(packed), ptr(flat), ptr(xc), ptr(dc), M, ptr(rgb), ptr(sigma), ptr(saved),
+            size = _hip.load().nr_mlp_frozen_saved_bytes if frozen else _hip.load().nr_mlp_saved_bytes
+            saved = torch.empty(int(size(cfg, M)), device=xc.device, dtype=torch.uint8)
+        call("nr_mlp_forward_frozen" if frozen and M > 0 else "nr_mlp_forward", cfg, ptr(packed), ptr(flat), ptr(xc), ptr(dc), M, ptr(rgb), ptr(sigma), ptr(saved),
              _hip.stream_ptr(), tag=f"[M={M}]")
         if training:
             ctx.save_for_backward(xc, dc if dc is not None else xc.new_empty(0), rgb, sigma)
             ctx.has_d = dc is not None
+            ctx.frozen = frozen
             ctx.keep = (net, saved, packed, flat, w_pos, w_dir)
             ctx.shapes = [p.shape for p in params]
         return rgb, sigma
@@ -212,6 +220,17 @@ class _MLPFunction(torch.autograd.Function):
         dev = xc.device
         g_rgb = ops._c(g_rgb) if g_rgb is not None else torch.zeros(M, 3, device=dev)
         g_sigma = ops._c(g_sigma) if g_sigma is not None else torch.zeros(M, 1, device=dev)
+        if ctx.frozen:
+            # no parameter gradient: _last_gflat, the gradient hook and the tile counts stay as they are
+            g_x = torch.empty(M, 3, device=dev) if ctx.needs_input_grad[0] else None
+            g_d = torch.empty(M, 3, device=dev) if (ctx.needs_input_grad[1] and ctx.has_d) else None
+            if M > 0:
+                ws = torch.empty(int(_hip.load().nr_mlp_frozen_workspace_bytes(cfg, M)), device=dev,
+                                 dtype=torch.uint8)
+                call("nr_mlp_backward_input", cfg, ptr(packed), ptr(flat), ptr(xc), ptr(dc) if ctx.has_d else None, M,
+                     ptr(rgb), ptr(sigma), ptr(saved), ptr(g_rgb), ptr(g_sigma), ptr(g_x), ptr(g_d), ptr(ws),
+                     _hip.stream_ptr(), tag=f"[M={M}]")
+            return (g_x, g_d, None, *([None] * len(ctx.shapes)))
         gflat = torch.empty(net._param_count, device=dev, dtype=torch.float32)
         g_x = torch.empty(M, 3, device=dev) if ctx.needs_input_grad[0] else None
         g_d = torch.empty(M, 3, device=dev) if (ctx.needs_input_grad[1] and ctx.has_d) else None
