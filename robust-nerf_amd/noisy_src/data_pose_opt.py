@@ -100,7 +100,7 @@ class PixelSampler:
         (``nr_gather_pixels``) turns the drawn indices into the batch: the values of the
         reference's three table gathers, bit for bit.  ``out``: preallocated
         (image_indices, pixel_coords, target_rgb) tensors the kernel writes in place (the
-        static inputs of ``engine.GraphedPoseTrainer``); the batch then holds them."""
+        static inputs of ``graphed.GraphedPoseTrainer``); the batch then holds them."""
         idx = torch.randint(0, self.n_pixels, (self.batch_size,), device=self.device, generator=generator)
         img, pix, rgb = ops.gather_pixels(idx, self.dataset.images, validate=False, out=out)
         return PixelBatch(image_indices=img, pixel_coords=pix, target_rgb=rgb, in_range=True)

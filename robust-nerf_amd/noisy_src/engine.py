@@ -8,7 +8,8 @@ LambdaLR 0.1^(step/(lr_decay*1000)).  Losses stay on the device; callers that
 log them call ``.item()`` themselves (the reference syncs four times a step).
 For data parallelism each network's flat gradient is all-reduced (RCCL) as soon
 as its backward has produced it (the fine net's overlaps the coarse backward),
-and the optimizer step waits for both.
+and the optimizer step waits for both.  The hipGraph replays of these
+steps live in ``graphed`` (GraphedTrainer, GraphedPoseTrainer; re-exported here).
 """
 
 from __future__ import annotations
@@ -18,6 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
+from .graphed import GraphedPoseTrainer, GraphedTrainer  # noqa: F401  (the public names of this module)
 from .optim import FusedAdam
 from .rendering import render_rays
 
@@ -186,6 +188,36 @@ class GradAllReducer:
         return {"steps": len(span), "span_ms": sum(span) / len(span), "exposed_ms": sum(exposed) / len(exposed)}
 
 
+def _hooked_reducer(process_group, nets) -> Optional[GradAllReducer]:
+    """The trainers' reducer (None for a single process): each network's backward hands
+    it the flat gradient as soon as it exists (``_grad_ready_hook``)."""
+    if process_group is None:
+        return None
+    reducer = GradAllReducer(process_group, average=False)
+    for net in nets:
+        if net is not None:
+            net._grad_ready_hook = reducer.launch
+    return reducer
+
+
+def _finish_and_adopt(reducer: GradAllReducer, nets, flats) -> None:
+    """Wait for the pending all-reduces; ``flats``: the networks' flat gradients among them."""
+    reducer.finish()
+    for net in nets:
+        if net is not None:
+            _adopt_reduced_grad(net, flats)
+
+
+def _loss_and_metrics(out):
+    """(loss_coarse [+ loss_fine], their detached values) of ``render_rays``' output."""
+    loss = out["loss_coarse"]
+    metrics = {"loss_coarse": loss.detach()}  # metrics hold no autograd graph
+    if "loss_fine" in out:
+        loss = loss + out["loss_fine"]
+        metrics["loss_fine"] = out["loss_fine"].detach()
+    return loss, metrics
+
+
 class Trainer:
     """One reference training iteration (train.py:68-119) on the HIP kernels.
     ``coarse_stream``: run the coarse network's forward, compositing, loss and backward on
@@ -220,12 +252,7 @@ class Trainer:
         self.optimizer = FusedAdam(params, lr=lr)
         self.scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimizer, lr_lambda_factory(lr_decay))
         self.process_group = process_group
-        self.reducer = None
-        if process_group is not None:
-            self.reducer = GradAllReducer(process_group, average=False)
-            for net in (model_coarse, model_fine):
-                if net is not None:
-                    net._grad_ready_hook = self.reducer.launch
+        self.reducer = _hooked_reducer(process_group, (model_coarse, model_fine))
 
     def step(self, rays_o: torch.Tensor, rays_d: torch.Tensor, target_rgb: torch.Tensor,
              t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -274,160 +301,16 @@ class Trainer:
             main.wait_stream(cs)  # join the coarse chain
             metrics = {"loss_coarse": loss_c, "loss_fine": lf}
         else:
-            loss_c = out["loss_coarse"]
-            loss = loss_c
-            metrics = {"loss_coarse": loss_c.detach()}  # metrics hold no autograd graph
-            if "loss_fine" in out:
-                loss_f = out["loss_fine"]
-                loss = loss_c + loss_f
-                metrics["loss_fine"] = loss_f.detach()
+            loss, metrics = _loss_and_metrics(out)
             loss.backward(ops.unit_grad(loss.device))
         if self.reducer is not None:
-            flats = [flat for _, flat in self.reducer.pending]
-            self.reducer.finish()
-            for net in (self.model_coarse, self.model_fine):
-                if net is not None:
-                    _adopt_reduced_grad(net, flats)
+            _finish_and_adopt(self.reducer, (self.model_coarse, self.model_fine),
+                              [flat for _, flat in self.reducer.pending])
         self.optimizer.step(clip_groups=[(self.params, self.max_norm)])
         self.scheduler.step()
         metrics["loss"] = loss.detach()
         metrics["rgb_fine"] = out.get("rgb_fine", out["rgb_coarse"]).detach()
         return metrics
-
-
-class GraphedTrainer:
-    """``Trainer.step`` captured once into a hipGraph (``torch.cuda.graph``) and replayed:
-    the ~23 kernels of a step become one graph launch, so a step costs its GPU time even
-    where the host's Python dispatch (autograd, the optimizer's bookkeeping: ~1.3 ms per
-    step) exceeds it -- small per-GPU batches such as BASELINE cfg #4's 512 rays per rank.
-
-    Everything the replay needs is on the device: the rays go through static input
-    buffers, the jitter / inverse-CDF uniforms are drawn by torch.rand into static
-    buffers before each replay (or the caller passes them; torch's graph-safe RNG inside
-    the graph when the step also draws noise), the fused Adam launch rewrites the packed
-    images, and the two step-dependent Adam scalars come from an 8-byte device pair
-    written before each replay (``FusedAdam.device_sched``); the LR schedule and the
-    optimizer's step counters advance on the host exactly as in ``Trainer.step``.
-    Data parallel: the trainer's RCCL all-reduces (one per network) are captured inside
-    the graph in their stream-ordered form, so a replay is the whole DP step.
-
-    The graph holds raw device addresses: every network's packed images and pack table
-    and the optimizer's flat m / v buffers.  Those tensors are pinned here, and a replay
-    after any of them was replaced (a checkpoint load, ``FusedAdam.load_state_dict``)
-    raises instead of writing into freed memory."""
-
-    def __init__(self, trainer: "Trainer", rays_o: torch.Tensor, rays_d: torch.Tensor, target_rgb: torch.Tensor,
-                 t_rand: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None, warmup: int = 2):
-        self.trainer = trainer
-        self._refuse_window()
-        opt = trainer.optimizer
-        self._adam = _AdamSchedule(opt, trainer.scheduler, rays_o.device, "trainer")
-        self.static = [t.detach().clone() for t in (rays_o, rays_d, target_rgb)]
-        self.static_rand = [None if t is None else t.detach().clone() for t in (t_rand, u)]
-        dev = rays_o.device
-        # randoms the caller does not inject are drawn into static buffers right before
-        # each step (eager warm-ups and every replay) rather than inside the graph: the
-        # same torch.rand calls in the same order as the eager step makes them, so the
-        # numbers are the eager step's, and a replay skips torch's graph-RNG prologue
-        # (two fill launches before every replay of a graph that draws).  Only when the
-        # step draws nothing else (raw_noise_std == 0), which would interleave with them
-        rc = trainer.render_config
-        self._predraw = []
-        if t_rand is None and u is None and rc.perturb and not rc.raw_noise_std:
-            B = rays_o.shape[0]
-            self.static_rand[0] = torch.empty(B, rc.num_samples, device=dev)
-            self._predraw.append(self.static_rand[0])
-            if rc.use_hierarchical and trainer.model_fine is not None:
-                self.static_rand[1] = torch.empty(B, rc.num_samples_fine, device=dev)
-                self._predraw.append(self.static_rand[1])
-        # eager warm-up steps on a side stream (allocator pools, optimizer state, packed
-        # images and pack tables exist before the capture); they are real training steps.
-        # warmup=0 is accepted once the trainer has stepped eagerly (the state exists):
-        # the capture then trains on nothing, so a caller's step sequence is unchanged
-        if warmup < 1 and not self._adam.step_states():
-            warmup = 1
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._draw()
-                trainer.step(*self.static, *self.static_rand)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        # capture one step; its host-side bookkeeping (Adam step counters, LR scheduler)
-        # ran once without device work, so it is rolled back afterwards
-        self._adam.common_step()
-        snap = self._adam.snapshot()
-        opt.device_sched = self._adam.pair
-        self.graph = torch.cuda.CUDAGraph()
-        # data parallel: the process group's watchdog thread polls the events of the eager
-        # warm-up's all-reduces until it has seen them complete.  Under the default "global"
-        # capture mode such a query from another thread fails while the capture is open,
-        # and the watchdog then ends the process; "thread_local" checks this thread only
-        mode = "thread_local" if trainer.process_group is not None else "global"
-        with torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.out = trainer.step(*self.static, *self.static_rand)
-        self._adam.restore(snap)
-        # the graph holds the pair's address; eager steps between replays (a batch of
-        # another shape, see train.train) use the host scalars again
-        opt.device_sched = None
-        self._bound = self._bound_buffers()
-
-    def _refuse_window(self) -> None:
-        # a replay rewrites the images' encoding columns unfolded behind the host's back,
-        # and this class does not stage window weights: only GraphedPoseTrainer does
-        for n in (self.trainer.model_coarse, self.trainer.model_fine):
-            if n is not None and n._pe_window.on:
-                raise ValueError("GraphedTrainer does not support a positional-encoding window (NeRF.set_pe_window): "
-                                 "use the eager Trainer, or GraphedPoseTrainer")
-
-    def _draw(self) -> None:
-        for t in self._predraw:
-            t.uniform_()  # torch.rand(shape) of the eager step, into the static buffer
-
-    def _bound_buffers(self):
-        """The device tensors whose addresses the captured graph holds (strong references)."""
-        nets = [n for n in (self.trainer.model_coarse, self.trainer.model_fine) if n is not None]
-        out = [t for n in nets for t in (n._packed, n._table, n._flat) if t is not None]
-        for m, v in self.trainer.optimizer._flat_state.values():
-            out += [m, v]
-        return out
-
-    def _check_bound(self) -> None:
-        now = self._bound_buffers()
-        if len(now) != len(self._bound) or any(a is not b for a, b in zip(now, self._bound)):
-            raise RuntimeError("GraphedTrainer: a buffer the captured graph writes was replaced (packed images, "
-                               "pack table, parameters or Adam state, e.g. by a checkpoint load); "
-                               "build a new GraphedTrainer")
-
-    def step(self, rays_o: Optional[torch.Tensor] = None, rays_d: Optional[torch.Tensor] = None,
-             target_rgb: Optional[torch.Tensor] = None, t_rand: Optional[torch.Tensor] = None,
-             u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """Replay one training step on these rays (copied into the static buffers; None:
-        the buffers as they are).  Returns the captured metrics (device tensors that every
-        replay overwrites).  Eager ``trainer.step`` calls may be interleaved (same state)."""
-        if self._predraw and (t_rand is None) != (u is None) and len(self._predraw) == 2:
-            raise ValueError("GraphedTrainer: inject both t_rand and u, or neither")
-        dsts, srcs = [], []
-        for dst, src in zip(self.static + self.static_rand, (rays_o, rays_d, target_rgb, t_rand, u)):
-            if src is not None:
-                if dst is None:
-                    raise ValueError("GraphedTrainer: t_rand / u were drawn in the graph at capture")
-                dsts.append(dst)
-                srcs.append(src)
-        if dsts and all(x.is_cuda and x.device == d.device and x.dtype == d.dtype and x.shape == d.shape
-                        for d, x in zip(dsts, srcs)):
-            torch._foreach_copy_(dsts, srcs)  # one launch for all the static inputs
-        else:
-            for d, x in zip(dsts, srcs):
-                d.copy_(x)
-        if self._predraw and t_rand is None:
-            self._draw()
-        self._check_bound()
-        self._refuse_window()
-        self._adam.write_next()
-        self.graph.replay()
-        self._adam.advance()
-        return self.out
 
 
 class PoseTrainer:
@@ -474,12 +357,7 @@ class PoseTrainer:
         self.scheduler_nerf = torch.optim.lr_scheduler.LambdaLR(self.optimizer_nerf, lam)
         self.scheduler_poses = (torch.optim.lr_scheduler.LambdaLR(self.optimizer_poses, lam)
                                 if self.optimizer_poses is not None else None)
-        self.reducer = None
-        if process_group is not None:
-            self.reducer = GradAllReducer(process_group, average=False)
-            for net in (model_coarse, model_fine):
-                if net is not None:
-                    net._grad_ready_hook = self.reducer.launch
+        self.reducer = _hooked_reducer(process_group, (model_coarse, model_fine))
 
     def set_pe_windows(self, iteration: int) -> None:
         """Both networks' windows of ``iteration`` under ``pe_schedule`` (no-op without one)."""
@@ -509,13 +387,7 @@ class PoseTrainer:
         # the MSE losses (train_pose_opt.py:355-370) come out of the compositing
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
                           t_rand=t_rand, u=u, target_rgb=target, loss_scale=gs)
-        loss_c = out["loss_coarse"]
-        loss = loss_c
-        metrics = {"loss_coarse": loss_c.detach()}  # metrics hold no autograd graph
-        if "loss_fine" in out:
-            loss_f = out["loss_fine"]
-            loss = loss_c + loss_f
-            metrics["loss_fine"] = loss_f.detach()
+        loss, metrics = _loss_and_metrics(out)
         bwd = loss
         if optimize_poses:
             # the regulariser is replicated on every rank: its gradient carries the seed's
@@ -535,10 +407,7 @@ class PoseTrainer:
             pflat = torch.cat([g.reshape(-1) for g in pg]) if pg else None
             if pflat is not None:
                 self.reducer.launch(pflat)
-            self.reducer.finish()
-            for net in (self.model_coarse, self.model_fine):
-                if net is not None:
-                    _adopt_reduced_grad(net, flats)
+            _finish_and_adopt(self.reducer, (self.model_coarse, self.model_fine), flats)
             off = 0
             for g in pg:
                 g.copy_(pflat[off:off + g.numel()].view(g.shape))
@@ -606,281 +475,13 @@ class PoseRefiner:
         rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses)
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
                           t_rand=t_rand, u=u, target_rgb=pixel_batch.target_rgb)
-        loss = out["loss_coarse"]
-        metrics = {"loss_coarse": loss.detach()}
-        if "loss_fine" in out:
-            metrics["loss_fine"] = out["loss_fine"].detach()
-            loss = loss + out["loss_fine"]
+        loss, metrics = _loss_and_metrics(out)
         loss.backward(ops.unit_grad(loss.device))
         self.optimizer_poses.step(clip_groups=[(self.poses, self.max_norm)])
         if self.scheduler_poses is not None:
             self.scheduler_poses.step()
         metrics["loss"] = loss.detach()
         return metrics
-
-
-class _AdamSchedule:
-    """One FusedAdam's share of a captured step (GraphedTrainer, GraphedPoseTrainer): the
-    8-byte device pair its Adam launch reads (``FusedAdam.device_sched``), the pinned
-    staging ring the pair is written through, and the host bookkeeping (step counters,
-    LambdaLR) a replay advances."""
-
-    RING = 64
-
-    def __init__(self, optimizer: FusedAdam, scheduler, device, what: str):
-        if not isinstance(optimizer, FusedAdam) or len(optimizer.param_groups) != 1:
-            raise ValueError(f"a graphed step needs a single-group FusedAdam for the {what}")
-        self.optimizer, self.scheduler, self.what = optimizer, scheduler, what
-        self.pair = torch.zeros(2, device=device, dtype=torch.float32)
-        # a slot is rewritten only after the copy that read it has run (its event),
-        # however far the host runs ahead
-        self._ring = torch.zeros(self.RING, 2, dtype=torch.float32).pin_memory()
-        self._ring_ev = [None] * self.RING
-        self._k = 0
-
-    def step_states(self):
-        opt = self.optimizer
-        seen, out = set(), []
-        for p in opt.param_groups[0]["params"]:
-            st = opt.state.get(p)
-            if st and "step" in st and id(st["step"]) not in seen:
-                seen.add(id(st["step"]))
-                out.append(st)
-        return out
-
-    def ready(self) -> bool:
-        """An eager step has created the flat m / v buffers and the step counters (a
-        capture would otherwise allocate and zero them inside the graph)."""
-        opt = self.optimizer
-        return bool(opt._flat_state) and all("step" in opt.state.get(p, ()) for p in opt.param_groups[0]["params"])
-
-    def common_step(self) -> int:
-        """The one Adam step count every buffer shares (one pair of bias corrections
-        drives every span of the captured launch)."""
-        vals = {int(st["step"]) for st in self.step_states()}
-        if len(vals) != 1:
-            raise RuntimeError(f"graphed step: the {self.what} optimizer's buffers are at different steps "
-                               f"{sorted(vals)}")
-        return vals.pop()
-
-    def snapshot(self):
-        return ([(st, st["step"].clone()) for st in self.step_states()], self.scheduler.state_dict(),
-                [g["lr"] for g in self.optimizer.param_groups])
-
-    def restore(self, snap) -> None:
-        steps, sched_state, lr = snap
-        for st, v in steps:
-            st["step"].copy_(v)
-        self.scheduler.load_state_dict(sched_state)
-        for g, v in zip(self.optimizer.param_groups, lr):
-            g["lr"] = v
-
-    def write_next(self) -> None:
-        """Stage the pair of the step about to be replayed (stream-ordered before it)."""
-        group = self.optimizer.param_groups[0]
-        b1, b2 = group["betas"]
-        a, b = ops.adam_sched_values(group["lr"], b1, b2, self.common_step() + 1)
-        slot = self._k % self.RING
-        if self._ring_ev[slot] is not None:
-            self._ring_ev[slot].synchronize()
-        self._ring[slot, 0], self._ring[slot, 1] = a, b  # fp32 rounding, as the host path's
-        self.pair.copy_(self._ring[slot], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._ring_ev[slot] = ev
-        self._k += 1
-
-    def advance(self) -> None:
-        """What ``optimizer.step(); scheduler.step()`` do on the host."""
-        for st in self.step_states():
-            st["step"] += 1
-        self.scheduler.step()
-
-
-class GraphedPoseTrainer:
-    """``PoseTrainer.step`` replayed from hipGraphs: the counterpart of ``GraphedTrainer``
-    for the joint pose-optimisation step (BASELINE cfg #3), bit-identical to the eager step.
-
-    The step has two shapes, and each gets its own graph, captured on its first use: with
-    frozen poses (``optimize_poses=False``: the poses enter detached, so there is no
-    input-gradient pass and no pose Adam) and optimising.  Both read one set of static
-    inputs: the pixel batch (``self.static``: image_indices, pixel_coords, target_rgb --
-    ``PixelSampler.sample_batch(out=self.static)`` writes a batch straight into them) and
-    the jitter / inverse-CDF uniforms (``self.static_rand``).  As in ``GraphedTrainer``,
-    randoms the caller does not inject are drawn by torch.rand into the static buffers
-    before each step, in the eager step's order (no RNG inside the graph unless the step
-    also draws noise).  Each optimizer has its own device schedule pair, written before a
-    replay; the Adam step counters and both LambdaLRs advance on the host exactly as in
-    ``PoseTrainer.step`` (the pose optimizer's only on optimising steps).
-
-    A coarse-to-fine window (``PoseTrainer.pe_schedule``, or ``NeRF.set_pe_window`` between
-    steps) lives in each network's persistent window tensor, which the captured fold and
-    gradient-scaling launches read: it is written before a replay, never inside the graph.
-
-    Every call of ``step`` is one training step of the caller's sequence.  The first
-    ``warmup`` calls of a shape run eagerly (on the static buffers); so does any call
-    while that shape's Adam state does not exist yet -- the optimising graph can only be
-    captured after one eager optimising step has created the pose Adam's m / v -- and the
-    call after them captures and replays.  The capture is single-stream (``PoseTrainer``
-    has no coarse stream).  Data parallel: the network all-reduces and the pose-gradient
-    all-reduce are captured (RCCL only).
-
-    The graphs hold raw device addresses: both networks' packed images, pack tables and
-    parameters, the pose parameters and both optimizers' flat m / v buffers.  A replay
-    after any of them was replaced (a checkpoint load, ``FusedAdam.load_state_dict``)
-    raises instead of writing into freed memory."""
-
-    def __init__(self, trainer: "PoseTrainer", pixel_batch, t_rand: Optional[torch.Tensor] = None,
-                 u: Optional[torch.Tensor] = None, warmup: int = 2):
-        from .data_pose_opt import PixelBatch
-        self.trainer = trainer
-        self.warmup = int(warmup)
-        self._require_in_range(pixel_batch)
-        dev = pixel_batch.target_rgb.device
-        if trainer.reducer is not None:
-            # the captured step contains the all-reduces: only RCCL collectives are capturable
-            backend = trainer.reducer.dist.get_backend(trainer.reducer.group)
-            if backend != "nccl":
-                raise ValueError("GraphedPoseTrainer with data parallelism needs the nccl (RCCL) backend, "
-                                 f"not {backend}")
-        self._nerf = _AdamSchedule(trainer.optimizer_nerf, trainer.scheduler_nerf, dev, "network")
-        self._poses = (_AdamSchedule(trainer.optimizer_poses, trainer.scheduler_poses, dev, "pose")
-                       if trainer.optimizer_poses is not None else None)
-        self.static = [pixel_batch.image_indices.detach().to(torch.int64).clone(),
-                       pixel_batch.pixel_coords.detach().float().clone(),
-                       pixel_batch.target_rgb.detach().float().clone()]
-        self.batch = PixelBatch(*self.static, in_range=True)
-        self.static_rand = [None if t is None else t.detach().clone() for t in (t_rand, u)]
-        # see GraphedTrainer: pre-drawn randoms, only when the step draws nothing else
-        rc = trainer.render_config
-        self._predraw = []
-        if t_rand is None and u is None and rc.perturb and not rc.raw_noise_std:
-            B = self.static[0].shape[0]
-            self.static_rand[0] = torch.empty(B, rc.num_samples, device=dev)
-            self._predraw.append(self.static_rand[0])
-            if rc.use_hierarchical and trainer.model_fine is not None:
-                self.static_rand[1] = torch.empty(B, rc.num_samples_fine, device=dev)
-                self._predraw.append(self.static_rand[1])
-        self._graphs = {}  # optimising (bool) -> (graph, captured metrics, bound buffers)
-        self._eager_steps = {False: 0, True: 0}
-
-    @staticmethod
-    def _require_in_range(pixel_batch) -> None:
-        if not pixel_batch.in_range:
-            # the validating ray kernel's flag is read on the host: not capturable
-            raise ValueError("GraphedPoseTrainer: the pixel batch must have in_range=True (PixelSampler.sample_batch; "
-                             "validate other batches with ops.check_index_range first)")
-
-    def _scheds(self, optimizing: bool):
-        return [self._nerf] + ([self._poses] if optimizing else [])
-
-    def _bound_buffers(self, optimizing: bool):
-        """(tensor, address) of everything the captured graph reads or writes in place."""
-        tr = self.trainer
-        nets = [n for n in (tr.model_coarse, tr.model_fine) if n is not None]
-        ts = [t for n in nets for t in (n._packed, n._table, n._flat) if t is not None]
-        # a captured step folds the window tensors it saw (or none): both must still hold
-        ts += [w for n in nets if n._flat is not None for w in n._pe_window.device_weights(n._flat.device)
-               if w is not None]
-        ts += list(tr.camera_params.parameters())
-        for s in self._scheds(optimizing):
-            for m, v in s.optimizer._flat_state.values():
-                ts += [m, v]
-        return [(t, t.data_ptr()) for t in ts]
-
-    def _check_bound(self, optimizing: bool, bound) -> None:
-        now = self._bound_buffers(optimizing)
-        if len(now) != len(bound) or any(a is not b or pa != pb for (a, pa), (b, pb) in zip(now, bound)):
-            raise RuntimeError("GraphedPoseTrainer: a buffer the captured graph writes was replaced (packed images, "
-                               "pack table, parameters, poses or Adam state, e.g. by a checkpoint load), or a "
-                               "positional-encoding window was added or removed; build a new GraphedPoseTrainer")
-
-    def _capture(self, optimizing: bool):
-        tr = self.trainer
-        scheds = self._scheds(optimizing)
-        for s in scheds:
-            s.common_step()
-        # the capture runs the step's host bookkeeping once without device work: rolled back
-        snaps = [s.snapshot() for s in scheds]
-        graph = torch.cuda.CUDAGraph()
-        # data parallel: see GraphedTrainer (the process group's watchdog thread queries
-        # events while the capture is open)
-        mode = "thread_local" if tr.reducer is not None else "global"
-        for s in scheds:
-            s.optimizer.device_sched = s.pair
-        try:
-            with torch.cuda.graph(graph, capture_error_mode=mode):
-                out = tr.step(self.batch, optimize_poses=optimizing, t_rand=self.static_rand[0],
-                              u=self.static_rand[1])
-        finally:
-            for s, snap in zip(scheds, snaps):
-                # eager steps between replays use the host scalars again
-                s.optimizer.device_sched = None
-                s.restore(snap)
-        entry = (graph, out, self._bound_buffers(optimizing))
-        self._graphs[optimizing] = entry
-        return entry
-
-    def step(self, pixel_batch=None, optimize_poses: bool = True, t_rand: Optional[torch.Tensor] = None,
-             u: Optional[torch.Tensor] = None, iteration: Optional[int] = None) -> Dict[str, torch.Tensor]:
-        """One training step on this batch (copied into the static buffers; None, or the
-        batch ``sample_batch(out=self.static)`` returned: the buffers as they are).
-        ``iteration`` sets the windows of ``PoseTrainer.pe_schedule`` first.  Returns
-        the metrics of the graph it replayed (device tensors that every replay of that
-        graph overwrites).  Eager ``trainer.step`` calls may be interleaved (same state)."""
-        if self._predraw and (t_rand is None) != (u is None) and len(self._predraw) == 2:
-            raise ValueError("GraphedPoseTrainer: inject both t_rand and u, or neither")
-        optimizing = bool(optimize_poses) and self._poses is not None
-        srcs = [None] * 3
-        if pixel_batch is not None:
-            self._require_in_range(pixel_batch)
-            srcs = [pixel_batch.image_indices, pixel_batch.pixel_coords, pixel_batch.target_rgb]
-        dsts, cps = [], []
-        for dst, src in zip(self.static + self.static_rand, srcs + [t_rand, u]):
-            if src is None or src is dst:
-                continue
-            if dst is None:
-                raise ValueError("GraphedPoseTrainer: t_rand / u were drawn in the graph at capture")
-            if src.shape != dst.shape:
-                raise ValueError(f"GraphedPoseTrainer: input of shape {tuple(src.shape)} for the static buffer "
-                                 f"{tuple(dst.shape)}")
-            if src.is_cuda and src.device == dst.device and src.dtype == dst.dtype == torch.float32:
-                dsts.append(dst)
-                cps.append(src)
-            else:
-                dst.copy_(src)  # the int64 image indices
-        if dsts:
-            torch._foreach_copy_(dsts, cps)  # one launch for the fp32 static inputs
-        if self._predraw and t_rand is None:
-            for t in self._predraw:
-                t.uniform_()  # torch.rand(shape) of the eager step, into the static buffer
-        if iteration is not None:
-            self.trainer.set_pe_windows(iteration)
-        nets = [n for n in (self.trainer.model_coarse, self.trainer.model_fine) if n is not None]
-        for n in nets:
-            if n._flat is not None:
-                # the window tensors' pending values go out here, stream-ordered before the
-                # replay (as _AdamSchedule.write_next's pair), and never inside a capture
-                n._pe_window.device_weights(n._flat.device)
-        entry = self._graphs.get(optimizing)
-        if entry is None:
-            if self._eager_steps[optimizing] < self.warmup or not all(s.ready() for s in self._scheds(optimizing)):
-                self._eager_steps[optimizing] += 1
-                return self.trainer.step(self.batch, optimize_poses=optimizing, t_rand=self.static_rand[0],
-                                         u=self.static_rand[1])
-            entry = self._capture(optimizing)
-        graph, out, bound = entry
-        self._check_bound(optimizing, bound)
-        scheds = self._scheds(optimizing)
-        for s in scheds:
-            s.write_next()
-        graph.replay()
-        for s in scheds:
-            s.advance()
-        for n in nets:
-            # the replayed Adam rewrote the images' encoding columns unfolded, unseen by the host
-            n._fold_key = None
-        return out
 
 
 def _adopt_reduced_grad(net, flats) -> None:
@@ -903,18 +504,3 @@ def _adopt_reduced_grad(net, flats) -> None:
                 off += n
             del flats[next(i for i, x in enumerate(flats) if x is f)]  # by identity (== is elementwise)
             return
-
-
-def _flat_grad_of(net) -> torch.Tensor:
-    """The network's gradient as ONE flat tensor (the MLP backward writes it that way)."""
-    from .optim import _contiguous_run
-    grads = [p.grad for p in net.parameters()]
-    flat = _contiguous_run(grads)
-    if flat is None:
-        flat = torch.cat([g.reshape(-1) for g in grads])
-        off = 0
-        for p in net.parameters():
-            n = p.numel()
-            p.grad = flat[off:off + n].view(p.shape)
-            off += n
-    return flat

@@ -436,7 +436,7 @@ class NeRF(nn.Module):
             if nbytes < 0:
                 raise RuntimeError(f"NeRF config unsupported by the HIP MLP: {_hip.last_error()}")
             # re-pack into the existing images when they fit: a captured hipGraph
-            # (engine.GraphedTrainer) holds their address, so it stays valid
+            # (graphed.GraphedTrainer) holds their address, so it stays valid
             if (self._packed is None or self._packed.numel() != nbytes
                     or self._packed.device != self._flat.device):
                 self._packed = torch.empty(nbytes, device=self._flat.device, dtype=torch.uint8)

@@ -100,7 +100,7 @@ class FusedAdam(torch.optim.Optimizer):
         # refresh a NeRF's packed MFMA images inside the Adam launch (False: the next
         # forward re-packs them, the pre-fusion behaviour; tests compare the two)
         self.refresh_images = refresh_images
-        # graph mode (engine.GraphedTrainer): a device fp32 pair {lr/bc1, sqrt(bc2)} the
+        # graph mode (graphed.GraphedTrainer): a device fp32 pair {lr/bc1, sqrt(bc2)} the
         # Adam launch reads, so a captured step replays with the schedule advanced
         self.device_sched: Optional[torch.Tensor] = None
         # parameter lists that are whole NeRF networks, by the parameters' identities:

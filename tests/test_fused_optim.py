@@ -189,6 +189,48 @@ def test_graphed_trainer_equals_eager_trainer(precision):
     assert int(eager.optimizer.state[pe]["step"]) == int(tr_g.optimizer.state[pg]["step"]) == 7
 
 
+def test_graphed_trainer_refuses_on_the_host_and_advances_nothing():
+    """A (1, 3) rays_o, which copy_ would broadcast over the whole static buffer, is a
+    ValueError before anything is copied, drawn or advanced: the next valid replay's loss
+    is the eager twin's, bit for bit.  After ``optimizer.load_state_dict`` replaced the
+    Adam moments the graph writes, a replay raises instead of writing through the old
+    addresses.  Both refusals happen on the host, before any launch."""
+    from noisy_src.config import ModelConfig, RenderConfig
+    from noisy_src.engine import GraphedTrainer, Trainer
+    from noisy_src.model import create_nerf
+    rc = RenderConfig(num_samples=32, num_samples_fine=32)
+    trainers = []
+    for _ in range(2):
+        torch.manual_seed(17)
+        mc, mf = create_nerf(ModelConfig(precision="bf16"))
+        trainers.append(Trainer(mc.to(DEV), mf.to(DEV), rc))
+    eager, tr_g = trainers
+    g = torch.Generator().manual_seed(31)
+    B = 256
+
+    def batch():
+        o = torch.randn(B, 3, generator=g) * 0.1 + torch.tensor([0.0, 0.0, 4.0])
+        dd = torch.nn.functional.normalize(torch.randn(B, 3, generator=g) * 0.2 + torch.tensor([0.0, 0.0, -1.0]), dim=-1)
+        return [t.to(DEV) for t in (o, dd, torch.rand(B, 3, generator=g), torch.rand(B, rc.num_samples, generator=g),
+                                    torch.rand(B, rc.num_samples_fine, generator=g))]
+
+    b0, b1, b2 = batch(), batch(), batch()
+    graphed = GraphedTrainer(tr_g, *b0, warmup=1)
+    eager.step(*b0)
+    assert float(eager.step(*b1)["loss"]) == float(graphed.step(*b1)["loss"])
+    with pytest.raises(ValueError, match=r"\(1, 3\).*\(256, 3\)"):
+        graphed.step(b2[0][:1], *b2[1:])
+    assert torch.equal(graphed.static[1], b1[1])  # the valid inputs of the refused call were not staged
+    le, lg = float(eager.step(*b2)["loss"]), float(graphed.step(*b2)["loss"])
+    assert le == lg, (le, lg)
+    pe, pg = eager.params[0], tr_g.params[0]
+    assert int(eager.optimizer.state[pe]["step"]) == int(tr_g.optimizer.state[pg]["step"]) == 3
+    assert eager.optimizer.param_groups[0]["lr"] == tr_g.optimizer.param_groups[0]["lr"]
+    tr_g.optimizer.load_state_dict(tr_g.optimizer.state_dict())
+    with pytest.raises(RuntimeError, match="replaced"):
+        graphed.step(*b2)
+
+
 def test_graphed_trainer_draws_the_eager_randoms():
     """Without injected randoms, GraphedTrainer draws the jitter and inverse-CDF uniforms
     with torch.rand into its static buffers before each replay (no RNG inside the graph):
