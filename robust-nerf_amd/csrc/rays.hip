@@ -33,6 +33,16 @@ __global__ void ray_directions_kernel(int H, int W, float focal, float cx, float
     dirs[3 * p + 2] = -1.0f;
 }
 
+// The same table with a focal length per axis (learned intrinsics; no reference counterpart).
+__global__ void ray_directions_xy_kernel(int H, int W, float fx, float fy, float cx, float cy, float* dirs) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= H * W) return;
+    const int j = p / W, i = p % W;
+    dirs[3 * p + 0] = (static_cast<float>(i) - cx) / fx;
+    dirs[3 * p + 1] = -((static_cast<float>(j) - cy) / fy);
+    dirs[3 * p + 2] = -1.0f;
+}
+
 // rays_d = normalize(sum_k dir[k] * R[:,k]) (rays.py:89-94), rays_o = t.
 __device__ __forceinline__ void rotate_normalize(const float* R /*4x4 row-major*/, float dx, float dy,
                                                  float dz, float& ox, float& oy, float& oz) {
@@ -222,6 +232,143 @@ rays_from_pixels_bwd_kernel(const int64_t* img_idx, const float* pix, const floa
 __global__ void check_img_idx_kernel(const int64_t* img_idx, int B, int n_img, int* flag) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B && (img_idx[b] < 0 || img_idx[b] >= n_img)) flag[0] = 1;
+}
+
+// ------------------------------------------------- A3, learned intrinsics -
+// The same rays with a focal length per axis read from DEVICE memory (fxy = {fx, fy}): a
+// captured graph then sees the value of each replay, where a kernel argument would be
+// baked in at capture.  pixel_dir / rotate_normalize operation for operation, so that
+// fx == fy == focal gives the bits of rays_from_pixels_fwd_kernel.
+__device__ __forceinline__ void pixel_dir_xy(const float* pix, int b, int W, int H, float fx, float fy, float& dx,
+                                             float& dy) {
+    const int u = static_cast<int>(pix[2 * b]);
+    const int v = static_cast<int>(pix[2 * b + 1]);
+    dx = (static_cast<float>(u) - static_cast<float>(W) * 0.5f) / fx;
+    dy = -((static_cast<float>(v) - static_cast<float>(H) * 0.5f) / fy);
+}
+
+__global__ void rays_from_pixels_intr_fwd_kernel(const int64_t* img_idx, const float* pix, const float* poses,
+                                                 int n_img, int H, int W, const float* fxy, int B, float* ro,
+                                                 float* rd, int* bad_index) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t img = img_idx[b];
+    if (img < 0 || img >= n_img) {
+        for (int c = 0; c < 3; ++c) ro[3 * b + c] = rd[3 * b + c] = __builtin_nanf("");
+        if (bad_index) *bad_index = 1;
+        return;
+    }
+    const float* P = poses + 16 * img;
+    float dx, dy;
+    pixel_dir_xy(pix, b, W, H, fxy[0], fxy[1], dx, dy);
+    float x, y, z;
+    rotate_normalize(P, dx, dy, -1.0f, x, y, z);
+    rd[3 * b] = x;
+    rd[3 * b + 1] = y;
+    rd[3 * b + 2] = z;
+    ro[3 * b] = P[3];
+    ro[3 * b + 1] = P[7];
+    ro[3 * b + 2] = P[11];
+}
+
+// ray_pose_grad plus the ray's two focal terms cf = {dL/dfx, dL/dfy}: the cotangent gv of
+// v = R d taken back to the camera frame (g_d = R^T gv) times d(dx)/d(fx) = -dx/fx and
+// d(dy)/d(fy) = -dy/fy.  c[] is computed exactly as ray_pose_grad computes it.
+__device__ __forceinline__ void ray_pose_intr_grad(const float* P, const float* pix, int b, int W, int H, float fx,
+                                                   float fy, const float* g_ro, const float* g_rd, float c[12],
+                                                   float cf[2]) {
+    c[9] = g_ro[3 * b];
+    c[10] = g_ro[3 * b + 1];
+    c[11] = g_ro[3 * b + 2];
+    if (g_rd == nullptr) {
+        for (int e = 0; e < 9; ++e) c[e] = 0.f;
+        cf[0] = cf[1] = 0.f;
+        return;
+    }
+    float dx, dy;
+    pixel_dir_xy(pix, b, W, H, fx, fy, dx, dy);
+    const float dz = -1.0f;
+    const float vx = (dx * P[0] + dy * P[1]) + dz * P[2];
+    const float vy = (dx * P[4] + dy * P[5]) + dz * P[6];
+    const float vz = (dx * P[8] + dy * P[9]) + dz * P[10];
+    const float n = norm3(vx, vy, vz);
+    const float ux = vx / n, uy = vy / n, uz = vz / n;
+    const float gx = g_rd[3 * b], gy = g_rd[3 * b + 1], gz = g_rd[3 * b + 2];
+    const float dot = ux * gx + uy * gy + uz * gz;
+    const float gv[3] = {(gx - ux * dot) / n, (gy - uy * dot) / n, (gz - uz * dot) / n};
+    const float d3[3] = {dx, dy, dz};
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) c[3 * r + k] = gv[r] * d3[k];
+    const float g_dx = (P[0] * gv[0] + P[4] * gv[1]) + P[8] * gv[2];
+    const float g_dy = (P[1] * gv[0] + P[5] * gv[1]) + P[9] * gv[2];
+    cf[0] = g_dx * (-dx / fx);
+    cf[1] = g_dy * (-dy / fy);
+}
+
+// rays_from_pixels_bwd_kernel with two more accumulators through the same fixed tree:
+// g_poses as there (bit-identical for fx == fy), and this image's focal partial WRITTEN to
+// focal_part[img] (an image without rays in the batch: an exact 0).
+__global__ void __launch_bounds__(kPoseRedThreads)
+rays_from_pixels_intr_bwd_kernel(const int64_t* img_idx, const float* pix, const float* poses, int n_img, int H,
+                                 int W, const float* fxy, int B, const float* g_ro, const float* g_rd,
+                                 float* g_poses, float* focal_part) {
+    const int img = blockIdx.x;
+    const float* P = poses + 16 * static_cast<int64_t>(img);
+    const float fx = fxy[0], fy = fxy[1];
+    float acc[14];
+    for (int e = 0; e < 14; ++e) acc[e] = 0.f;
+    for (int b = threadIdx.x; b < B; b += kPoseRedThreads) {
+        if (img_idx[b] != img) continue;
+        float c[12], cf[2];
+        ray_pose_intr_grad(P, pix, b, W, H, fx, fy, g_ro, g_rd, c, cf);
+        for (int e = 0; e < 12; ++e) acc[e] += c[e];
+        acc[12] += cf[0];
+        acc[13] += cf[1];
+    }
+    __shared__ float part[14][kPoseRedThreads / 64];
+    for (int e = 0; e < 14; ++e) {
+        float s = acc[e];
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        if ((threadIdx.x & 63) == 0) part[e][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 14) {
+        const int e = threadIdx.x;
+        float t = 0.f;
+        for (int w = 0; w < kPoseRedThreads / 64; ++w) t += part[e][w];
+        if (e < 12) {
+            float* G = g_poses + 16 * static_cast<int64_t>(img);
+            G[e < 9 ? 4 * (e / 3) + (e % 3) : 4 * (e - 9) + 3] += t;
+        } else {
+            focal_part[2 * static_cast<int64_t>(img) + (e - 12)] = t;
+        }
+    }
+}
+
+// One workgroup: thread t sums the partials of images t, t + 256, ... in that order, then
+// the fixed tree over the threads.  Writes g_fxy[0..1] (n_img == 0: zeros).
+__global__ void __launch_bounds__(kPoseRedThreads)
+focal_grad_final_kernel(const float* focal_part, int n_img, float* g_fxy) {
+    float sx = 0.f, sy = 0.f;
+    for (int i = threadIdx.x; i < n_img; i += kPoseRedThreads) {
+        sx += focal_part[2 * i];
+        sy += focal_part[2 * i + 1];
+    }
+    __shared__ float part[2][kPoseRedThreads / 64];
+    for (int off = 32; off > 0; off >>= 1) {
+        sx += __shfl_xor(sx, off);
+        sy += __shfl_xor(sy, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        part[0][threadIdx.x >> 6] = sx;
+        part[1][threadIdx.x >> 6] = sy;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        float t = 0.f;
+        for (int w = 0; w < kPoseRedThreads / 64; ++w) t += part[threadIdx.x][w];
+        g_fxy[threadIdx.x] = t;
+    }
 }
 
 // ---------------------------------------------------------------- A4 -----
@@ -587,6 +734,15 @@ int nr_ray_directions(int H, int W, float focal, float cx, float cy, float* dirs
     return NR_OK;
 }
 
+int nr_ray_directions_xy(int H, int W, float fx, float fy, float cx, float cy, float* dirs, nr_stream_t stream) {
+    NR_REQUIRE(H > 0 && W > 0 && dirs, "nr_ray_directions_xy: bad arguments");
+    const int n = H * W;
+    hipLaunchKernelGGL(ray_directions_xy_kernel, dim3(ceil_div(n, 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), H, W, fx, fy, cx, cy, dirs);
+    NR_LAUNCH_CHECK("nr_ray_directions_xy");
+    return NR_OK;
+}
+
 int nr_get_rays(const float* dirs, const float* c2w, int64_t N, float* ro, float* rd, nr_stream_t stream) {
     NR_REQUIRE(dirs && c2w && ro && rd && N >= 0, "nr_get_rays: bad arguments");
     if (N == 0) return NR_OK;
@@ -635,6 +791,44 @@ int nr_rays_from_pixels_bwd(const int64_t* img_idx, const float* pix, const floa
                        static_cast<hipStream_t>(stream), img_idx, pix, poses, n_img, H, W, focal, B, g_ro, g_rd,
                        g_poses);
     NR_LAUNCH_CHECK("nr_rays_from_pixels_bwd");
+    return NR_OK;
+}
+
+int nr_rays_from_pixels_intr_fwd(const int64_t* img_idx, const float* pix, const float* poses, int n_img, int H,
+                                 int W, const float* fxy, int B, float* ro, float* rd, int* bad_index,
+                                 nr_stream_t stream) {
+    // an empty batch may come with null arrays (a zero-size tensor has no storage)
+    NR_REQUIRE(fxy && B >= 0 && n_img > 0 && (B == 0 || (img_idx && pix && poses && ro && rd)),
+               "nr_rays_from_pixels_intr_fwd: bad arguments");
+    if (B == 0) return NR_OK;
+    hipLaunchKernelGGL(rays_from_pixels_intr_fwd_kernel, dim3(ceil_div(B, 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), img_idx, pix, poses, n_img, H, W, fxy, B, ro, rd,
+                       bad_index);
+    NR_LAUNCH_CHECK("nr_rays_from_pixels_intr_fwd");
+    return NR_OK;
+}
+
+int64_t nr_rays_from_pixels_intr_bwd_workspace_bytes(int n_img) {
+    return static_cast<int64_t>(n_img > 0 ? n_img : 1) * 2 * sizeof(float);
+}
+
+int nr_rays_from_pixels_intr_bwd(const int64_t* img_idx, const float* pix, const float* poses, int n_img, int H,
+                                 int W, const float* fxy, int B, const float* g_ro, const float* g_rd,
+                                 float* g_poses, float* g_fxy, void* workspace, nr_stream_t stream) {
+    NR_REQUIRE(fxy && g_poses && g_fxy && workspace && B >= 0 && n_img > 0 &&
+                   (B == 0 || (img_idx && pix && poses && g_ro)),
+               "nr_rays_from_pixels_intr_bwd: bad arguments");
+    float* focal_part = static_cast<float*>(workspace);
+    if (B > 0) {
+        hipLaunchKernelGGL(rays_from_pixels_intr_bwd_kernel, dim3(n_img), dim3(kPoseRedThreads), 0,
+                           static_cast<hipStream_t>(stream), img_idx, pix, poses, n_img, H, W, fxy, B, g_ro, g_rd,
+                           g_poses, focal_part);
+        NR_LAUNCH_CHECK("nr_rays_from_pixels_intr_bwd");
+    }
+    // an empty batch has no partials: the final launch then writes zeros
+    hipLaunchKernelGGL(focal_grad_final_kernel, dim3(1), dim3(kPoseRedThreads), 0, static_cast<hipStream_t>(stream),
+                       focal_part, B > 0 ? n_img : 0, g_fxy);
+    NR_LAUNCH_CHECK("nr_rays_from_pixels_intr_bwd");
     return NR_OK;
 }
 

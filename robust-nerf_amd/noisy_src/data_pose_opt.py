@@ -75,14 +75,18 @@ class PixelDataset:
             self._pixel_coords = single.unsqueeze(0).expand(self.n_images, -1, -1).reshape(-1, 2)
         return self._pixel_coords
 
-    def get_rays_from_pixels(self, pixel_batch: PixelBatch, poses: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def get_rays_from_pixels(self, pixel_batch: PixelBatch, poses: torch.Tensor,
+                             fxy: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference data_pose_opt.py:83-148.  ``poses`` holds one pose per UNIQUE image of
-        the batch, in ascending image order (``poses_all[torch.unique(indices)]``)."""
+        the batch, in ascending image order (``poses_all[torch.unique(indices)]``).
+        ``fxy`` (optional, (2,) fp32 device tensor): learnable focal lengths (fx, fy) in place
+        of the dataset's ``focal`` (``ops.rays_from_pixels``)."""
         uniq, inv = torch.unique(pixel_batch.image_indices, return_inverse=True)
         if poses.shape[0] != uniq.shape[0]:
             raise ValueError(f"get_rays_from_pixels: {poses.shape[0]} poses for {uniq.shape[0]} unique images")
         # ``inv`` indexes ``uniq`` by construction: nothing to validate here
-        return ops.rays_from_pixels(inv, pixel_batch.pixel_coords, poses, self.H, self.W, self.focal, validate=False)
+        return ops.rays_from_pixels(inv, pixel_batch.pixel_coords, poses, self.H, self.W,
+                                    self.focal if fxy is None else fxy, validate=False)
 
 
 class PixelSampler:
@@ -105,13 +109,16 @@ class PixelSampler:
         img, pix, rgb = ops.gather_pixels(idx, self.dataset.images, validate=False, out=out)
         return PixelBatch(image_indices=img, pixel_coords=pix, target_rgb=rgb, in_range=True)
 
-    def get_rays_for_batch(self, pixel_batch: PixelBatch, poses: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def get_rays_for_batch(self, pixel_batch: PixelBatch, poses: torch.Tensor,
+                           fxy: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference data_pose_opt.py:200-223 with ``poses`` = every image's pose (N,4,4):
         the kernel indexes them by image directly (the reference's unique/select/loop
-        gives the same rays), and the pose gradient lands on every image in the batch."""
+        gives the same rays), and the pose gradient lands on every image in the batch.
+        ``fxy`` (optional, (2,) fp32 device tensor): learnable focal lengths (fx, fy) in place
+        of the dataset's ``focal``; they get a gradient too."""
         ds = self.dataset
-        return ops.rays_from_pixels(pixel_batch.image_indices, pixel_batch.pixel_coords, poses, ds.H, ds.W, ds.focal,
-                                    validate=not pixel_batch.in_range)
+        return ops.rays_from_pixels(pixel_batch.image_indices, pixel_batch.pixel_coords, poses, ds.H, ds.W,
+                                    ds.focal if fxy is None else fxy, validate=not pixel_batch.in_range)
 
 
 def create_pixel_dataset(data: BlenderData) -> Tuple[PixelDataset, PixelSampler]:

@@ -338,21 +338,32 @@ class PoseTrainer:
     ``pe_schedule`` (optional) makes the positional encoding coarse-to-fine (BARF): a
     callable ``(iteration, num_freqs) -> num_freqs weights``; a ``step`` that is given
     its ``iteration`` sets both networks' windows from it first (``NeRF.set_pe_window``,
-    the position and the direction encoder each with its own frequency count)."""
+    the position and the direction encoder each with its own frequency count).
+
+    ``intrinsics`` (optional, ``train_pose_opt.CameraIntrinsics``) learns the focal length
+    with the poses (NeRF--, Wang et al. 2021): the rays come from its ``fxy()`` tensor, read
+    by the ray kernels from device memory, and its ``log_scale`` joins the pose Adam as a
+    clip group of its own (0.1), with the pose learning rate, LambdaLR and delay; its
+    gradient is appended to the pose-gradient all-reduce.  At ``log_scale = 0`` the rays,
+    and with them the networks' and poses' updates, are those without it, bit for bit."""
 
     def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,
                  lr: float = 5e-4, pose_lr: float = 1e-4, lr_decay: int = 250,
                  rotation_reg_weight: float = 0.01, translation_reg_weight: float = 0.001, process_group=None,
-                 pe_schedule=None):
+                 pe_schedule=None, intrinsics=None):
         self.pe_schedule = pe_schedule
         self.model_coarse, self.model_fine = model_coarse, model_fine
         self.camera_params, self.pixel_sampler, self.render_config = camera_params, pixel_sampler, render_config
+        self.intrinsics = intrinsics
         self.coarse = list(model_coarse.parameters())
         self.fine = list(model_fine.parameters()) if model_fine is not None else []
         self.poses = list(camera_params.parameters())
+        self.focal = list(intrinsics.parameters()) if intrinsics is not None else []
         self.rot_w, self.trans_w = rotation_reg_weight, translation_reg_weight
         self.optimizer_nerf = FusedAdam(self.coarse + self.fine, lr=lr)
-        self.optimizer_poses = FusedAdam(self.poses, lr=pose_lr) if self.poses else None
+        # the focal length rides with the poses: same Adam, learning rate, schedule and delay
+        # (its own clip group); with no learnable pose it has the optimizer to itself
+        self.optimizer_poses = FusedAdam(self.poses + self.focal, lr=pose_lr) if self.poses + self.focal else None
         lam = lr_lambda_factory(lr_decay)
         self.scheduler_nerf = torch.optim.lr_scheduler.LambdaLR(self.optimizer_nerf, lam)
         self.scheduler_poses = (torch.optim.lr_scheduler.LambdaLR(self.optimizer_poses, lam)
@@ -381,7 +392,13 @@ class PoseTrainer:
         poses = cam.get_all_poses()
         if not optimize_poses:
             poses = poses.detach()
-        rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses)
+        if self.intrinsics is None:
+            rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses)
+        else:
+            # (fx, fy) as a device tensor the ray kernels read; detached before the delay, like the poses
+            fxy = self.intrinsics.fxy()
+            rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses,
+                                                                   fxy if optimize_poses else fxy.detach())
         target = pixel_batch.target_rgb
         gs = self.reducer.prescale if self.reducer is not None else 1.0  # DP: 1/world in the seed
         # the MSE losses (train_pose_opt.py:355-370) come out of the compositing
@@ -403,7 +420,8 @@ class PoseTrainer:
         bwd.backward(ops.unit_grad(loss.device))
         if self.reducer is not None:
             flats = [flat for _, flat in self.reducer.pending]
-            pg = [p.grad for p in self.poses if p.grad is not None] if optimize_poses else []
+            # the focal gradient rides at the end of the pose-gradient buffer: no collective of its own
+            pg = [p.grad for p in self.poses + self.focal if p.grad is not None] if optimize_poses else []
             pflat = torch.cat([g.reshape(-1) for g in pg]) if pg else None
             if pflat is not None:
                 self.reducer.launch(pflat)
@@ -416,7 +434,8 @@ class PoseTrainer:
         self.optimizer_nerf.step(clip_groups=groups)
         self.scheduler_nerf.step()
         if optimize_poses:
-            self.optimizer_poses.step(clip_groups=[(self.poses, 0.1)])
+            groups = [(self.poses, 0.1)] + ([(self.focal, 0.1)] if self.focal else [])
+            self.optimizer_poses.step(clip_groups=groups)
             self.scheduler_poses.step()
         metrics["loss"] = loss.detach()
         metrics["rgb_fine"] = out.get("rgb_fine", out["rgb_coarse"]).detach()
@@ -435,10 +454,14 @@ class PoseRefiner:
     no dW); ``close()`` or leaving the ``with`` block restores them.  ``camera_params``
     must use the small-angle Jacobian (``fixed_small_angle=True``): refinement starts at
     w = 0, where the reference's ``theta < 1e-6`` rule gives a rotation gradient of
-    exactly zero.  ``lr_decay`` (optional): the LambdaLR of the training loops."""
+    exactly zero.  ``lr_decay`` (optional): the LambdaLR of the training loops.
+    ``fxy`` (optional, (2,) fp32 device tensor): fixed focal lengths (fx, fy), e.g. those a
+    checkpoint learned, in place of the dataset's; the refiner does not learn intrinsics."""
 
     def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,
-                 pose_lr: float = 1e-3, max_norm: float = 0.1, lr_decay: Optional[int] = None):
+                 pose_lr: float = 1e-3, max_norm: float = 0.1, lr_decay: Optional[int] = None,
+                 fxy: Optional[torch.Tensor] = None):
+        self.fxy = fxy.detach() if fxy is not None else None
         if camera_params.learn_rotation and not camera_params.fixed_small_angle:
             raise ValueError("PoseRefiner needs CameraPoseParameters(fixed_small_angle=True): at w = 0 the "
                              "reference's theta < 1e-6 rule blocks the rotation gradient, so the poses could not turn")
@@ -472,7 +495,7 @@ class PoseRefiner:
              u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         self.optimizer_poses.zero_grad(set_to_none=True)
         poses = self.camera_params.get_all_poses()
-        rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses)
+        rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses, self.fxy)
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
                           t_rand=t_rand, u=u, target_rgb=pixel_batch.target_rgb)
         loss, metrics = _loss_and_metrics(out)

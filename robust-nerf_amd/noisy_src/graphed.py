@@ -351,7 +351,11 @@ class GraphedPoseTrainer:
                              "validate other batches with ops.check_index_range first)")
 
     def _bound_buffers(self, scheds):
-        return _bound_buffers(_nets(self.trainer), scheds, list(self.trainer.camera_params.parameters()))
+        # learned intrinsics add only their parameter: the ray kernels read (fx, fy) from device
+        # memory, recomputed from it inside the graph, so nothing of it is baked into a capture
+        intr = getattr(self.trainer, "intrinsics", None)
+        return _bound_buffers(_nets(self.trainer), scheds, list(self.trainer.camera_params.parameters())
+                              + (list(intr.parameters()) if intr is not None else []))
 
     def step(self, pixel_batch=None, optimize_poses: bool = True, t_rand: Optional[torch.Tensor] = None,
              u: Optional[torch.Tensor] = None, iteration: Optional[int] = None) -> Dict[str, torch.Tensor]:

@@ -76,6 +76,29 @@ def load_checkpoint(checkpoint_path: Path, device: str = "cuda", precision: Opti
     return NeRFRenderer(coarse, fine, render_cfg), cfg, ckpt.get("iteration", 0)
 
 
+def intrinsics_fxy(ckpt: dict):
+    """(fx, fy) a checkpoint learned (its ``intrinsics`` entry, written by ``train_pose_opt
+    --learn_focal``: focal_init * exp(log_scale) in fp32, as the training step computes it),
+    or None for a checkpoint without the entry, which renders with the dataset's focal length."""
+    state = ckpt.get("intrinsics")
+    if state is None:
+        return None
+    from .train_pose_opt import CameraIntrinsics
+    return CameraIntrinsics.from_state_dict({k: v.detach().cpu() for k, v in state.items()}).fxy_values()
+
+
+def _render(renderer, pose, H, W, focal, chunk_size, fxy):
+    """``render_image``; without learned focal lengths exactly the call of before."""
+    if fxy is None:
+        return render_image(renderer, pose, H, W, focal, chunk_size=chunk_size)
+    return render_image(renderer, pose, H, W, focal, chunk_size=chunk_size, fxy=fxy)
+
+
+def checkpoint_intrinsics(checkpoint_path: Path):
+    """``intrinsics_fxy`` of the checkpoint file at ``checkpoint_path``."""
+    return intrinsics_fxy(torch.load(checkpoint_path, map_location="cpu", weights_only=True))
+
+
 def save_image(img: torch.Tensor, path: Path) -> None:
     """Reference inference.py:108-111: [0,1] float (H,W,3) -> 8-bit PNG."""
     from PIL import Image
@@ -226,14 +249,15 @@ def checkpoint_train_poses(checkpoint_path: Path) -> torch.Tensor:
 
 def refine_view_poses(renderer: NeRFRenderer, test_data, poses: Dict[int, torch.Tensor], iters: int, lr: float = 1e-3,
                       rays_per_view: int = 256, chunk_size: int = 1024 * 4, seed: int = 0,
-                      log=print) -> Dict[int, torch.Tensor]:
+                      log=print, fxy=None) -> Dict[int, torch.Tensor]:
     """Photometric refinement of test poses on the frozen field: ``poses`` (view -> (4,4))
     are refined against their own images in groups of ``chunk_size // rays_per_view`` views,
     ``iters`` steps of ``engine.PoseRefiner`` per group with ``rays_per_view`` random pixels
     of every view of the group.  Sampling jitter follows the render config; the density
     noise of training (``raw_noise_std``) is off.  Every draw comes from a generator seeded
     with ``seed`` and the group's first view, so a view's result does not depend on the
-    groups before it."""
+    groups before it.  ``fxy`` (optional): learned focal lengths (fx, fy), used as fixed
+    values in place of ``test_data.focal``."""
     import dataclasses
     from types import SimpleNamespace
 
@@ -261,7 +285,9 @@ def refine_view_poses(renderer: NeRFRenderer, test_data, poses: Dict[int, torch.
             base = (torch.arange(len(group), device=dev) * (H * W)).repeat_interleave(rays_per_view)
             B = base.numel()
             first = last = None
-            with PoseRefiner(renderer.model_coarse, renderer.model_fine, cam, sampler, rc, pose_lr=lr) as refiner:
+            fxy_dev = torch.tensor(fxy, device=dev, dtype=torch.float32) if fxy is not None else None
+            with PoseRefiner(renderer.model_coarse, renderer.model_fine, cam, sampler, rc, pose_lr=lr,
+                             fxy=fxy_dev) as refiner:
                 for _ in range(iters):
                     idx = base + torch.randint(0, H * W, (B,), device=dev, generator=gen)
                     img, pix, rgb = ops.gather_pixels(idx, ds.images, validate=False)
@@ -285,7 +311,7 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
                       save_images: bool = True, log=print, fused_tail: bool = False, *,
                       view_indices: Optional[Sequence[int]] = None, mode: str = "test",
                       refine_iters: int = 0, refine_lr: float = 1e-3, refine_rays_per_view: int = 256,
-                      refine_seed: int = 0, align_train_poses=None) -> Dict[str, object]:
+                      refine_seed: int = 0, align_train_poses=None, fxy=None) -> Dict[str, object]:
     """Reference inference.py:145-318 (same per-image records, summary keys and files),
     sharded over ``process_group``'s ranks when one is given.  ``fused_tail``: the metrics
     of a view come from ``metrics.image_metrics`` (fp64 SSIM, one read-back) and its PNGs
@@ -299,7 +325,9 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
     (``refine_view_poses``; no collective).  With either, every per-image record gains
     ``pose_rotation_error_deg_before/after`` and ``pose_translation_error_before/after``
     (against the ground truth in the frame the view is rendered in) and
-    ``test_metrics.json`` a ``pose_refinement`` block; without, nothing changes."""
+    ``test_metrics.json`` a ``pose_refinement`` block; without, nothing changes.
+    ``fxy`` (optional): focal lengths (fx, fy) the checkpoint learned; the views are rendered
+    (and refined) with them instead of ``test_data.focal``."""
     rank, world = 0, 1
     if process_group is not None:
         import torch.distributed as dist
@@ -323,7 +351,7 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
     if refine_iters > 0:
         refined = refine_view_poses(renderer, test_data, {i: views[i][0] for i in order[rank::world]}, refine_iters,
                                     lr=refine_lr, rays_per_view=refine_rays_per_view, chunk_size=chunk_size,
-                                    seed=refine_seed, log=log)
+                                    seed=refine_seed, log=log, fxy=fxy)
     for i in order[rank::world]:
         pose, noise_info = views[i]
         pose_rec = {}
@@ -339,7 +367,7 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
             pose = after
         target = test_data.images[i]
         start = time.time()
-        out = render_image(renderer, pose, test_data.H, test_data.W, test_data.focal, chunk_size=chunk_size)
+        out = _render(renderer, pose, test_data.H, test_data.W, test_data.focal, chunk_size, fxy)
         pred = out["rgb"]
         torch.cuda.synchronize() if pred.is_cuda else None
         if fused_tail:
@@ -421,13 +449,14 @@ def _noisy_frame_poses(poses: torch.Tensor, noise_config: NoiseConfig):
 @torch.no_grad()
 def render_video(renderer: NeRFRenderer, poses: torch.Tensor, H: int, W: int, focal: float, output_dir: Path,
                  noise_config: NoiseConfig, fps: int = 30, chunk_size: int = 1024 * 4, *, process_group=None,
-                 fused_tail: bool = False, log=print) -> Path:
+                 fused_tail: bool = False, log=print, fxy=None) -> Path:
     """Reference inference.py:365-443: ``frames/frame_%04d.png``, ``video_config.json`` and,
     where ``ffmpeg`` runs, ``video.mp4`` (otherwise the frames directory is returned).
     Every frame's noise is drawn up front in frame order on every rank, so the poses equal
     the reference's sequential run; with a process group rank r renders frames r, r+N, ...
     and rank 0 alone writes the JSON and runs ``ffmpeg``.  ``fused_tail``: frames are
-    quantised on the device (``frame_u8``) and cross to the host as bytes."""
+    quantised on the device (``frame_u8``) and cross to the host as bytes.  ``fxy``
+    (optional): learned focal lengths (fx, fy) in place of ``focal``."""
     rank, world = 0, 1
     if process_group is not None:
         import torch.distributed as dist
@@ -442,7 +471,7 @@ def render_video(renderer: NeRFRenderer, poses: torch.Tensor, H: int, W: int, fo
         if noise_config.has_noise:
             log(f"  With noise: rot={noise_config.rotation_noise_deg}°, trans={noise_config.translation_noise}")
     for i in range(rank, n_frames, world):
-        rgb = render_image(renderer, frames[i][0], H, W, focal, chunk_size=chunk_size)["rgb"]
+        rgb = _render(renderer, frames[i][0], H, W, focal, chunk_size, fxy)["rgb"]
         path = frames_dir / f"frame_{i:04d}.png"
         if fused_tail:
             save_frame_u8(frame_u8(rgb), path)
@@ -534,6 +563,9 @@ def main(argv=None) -> None:
         log(f"Loading checkpoint: {a.checkpoint}")
         renderer, config, iteration = load_checkpoint(a.checkpoint, device, precision=a.precision)
         log(f"Loaded model from iteration {iteration}")
+        fxy = checkpoint_intrinsics(a.checkpoint)
+        if fxy is not None:
+            log(f"Learned focal lengths: fx {fxy[0]:.4f}, fy {fxy[1]:.4f} (used in place of the dataset's)")
         scene = a.scene or config.get("data", {}).get("scene_name", "lego")
         log(f"Scene: {scene}")
         if a.output_dir is None:
@@ -579,7 +611,7 @@ def main(argv=None) -> None:
                                   process_group=pg, log=log, fused_tail=fused, view_indices=only, mode=a.mode,
                                   refine_iters=a.refine_poses, refine_lr=a.refine_lr,
                                   refine_rays_per_view=a.refine_rays_per_view, refine_seed=a.refine_seed,
-                                  align_train_poses=align)
+                                  align_train_poses=align, fxy=fxy)
             log(f"\n{bar}\nTest Set Results:")
             log(f"  PSNR:  {m['psnr_mean']:.2f} ± {m['psnr_std']:.2f} dB")
             log(f"  SSIM:  {m['ssim_mean']:.4f} ± {m['ssim_std']:.4f}")
@@ -605,7 +637,8 @@ def main(argv=None) -> None:
             poses = create_spiral_poses(n_frames=a.n_frames, device=device)
             log("\nRendering video...")
             video_path = render_video(renderer, poses, data.H, data.W, data.focal, output_dir, noise_config, a.fps,
-                                      chunk_size=a.chunk_size, process_group=pg, fused_tail=fused, log=log)
+                                      chunk_size=a.chunk_size, process_group=pg, fused_tail=fused, log=log,
+                                      fxy=fxy)
             log(f"Video saved to: {video_path}")
         log("\nDone!")
     finally:
@@ -616,7 +649,7 @@ def main(argv=None) -> None:
 
 __all__ = ["load_checkpoint", "render_image", "save_image", "depth_to_colormap", "frame_u8", "depth_frame_u8",
            "save_frame_u8", "generate_output_folder_name", "create_spiral_poses", "evaluate_test_set", "render_video",
-           "checkpoint_train_poses", "refine_view_poses", "main"]
+           "checkpoint_train_poses", "refine_view_poses", "intrinsics_fxy", "checkpoint_intrinsics", "main"]
 
 if __name__ == "__main__":
     main()

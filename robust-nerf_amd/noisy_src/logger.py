@@ -33,6 +33,9 @@ class TrainingMetrics:
     learning_rate: float = 0.0
     time_per_iter: float = 0.0
     rays_per_sec: float = 0.0
+    # learned intrinsics only (train_pose_opt --learn_focal): mean |f / f_dataset - 1| in per
+    # cent; None leaves the reference's columns as they are
+    focal_error_pct: Optional[float] = None
 
     def to_dict(self) -> Dict[str, Any]:
         return {k: v for k, v in asdict(self).items() if v is not None}

@@ -46,6 +46,16 @@ def ray_directions(H: int, W: int, focal: float, cx: float, cy: float, device) -
     return out
 
 
+def ray_directions_xy(H: int, W: int, fx: float, fy: float, cx: float, cy: float, device) -> torch.Tensor:
+    """``ray_directions`` with a focal length per axis (learned intrinsics):
+    ((i - cx) / fx, -(j - cy) / fy, -1); with fx == fy the same bits."""
+    out = torch.empty(H, W, 3, device=device, dtype=_f32)
+    if not out.is_cuda:
+        _check(out)
+    call("nr_ray_directions_xy", H, W, float(fx), float(fy), float(cx), float(cy), ptr(out), _stream())
+    return out
+
+
 class _GetRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, directions, c2w):
@@ -464,6 +474,44 @@ class _RaysFromPixels(torch.autograd.Function):
         return None, None, g_poses, None, None, None, None
 
 
+class _RaysFromPixelsIntr(torch.autograd.Function):
+    """``_RaysFromPixels`` with the focal lengths ``fxy`` = (fx, fy) in device memory, read
+    when the kernels run (so a captured graph follows a focal length that changes every
+    step), and with a gradient for them beside the poses'."""
+
+    @staticmethod
+    def forward(ctx, img_idx, pix, poses, H, W, fxy, validate):
+        img = img_idx.to(torch.int64).contiguous()
+        px, ps = _c(pix), _c(poses)
+        B = img.shape[0]
+        ro = torch.empty(B, 3, device=px.device, dtype=_f32)
+        rd = torch.empty(B, 3, device=px.device, dtype=_f32)
+        flag = torch.zeros(1, device=px.device, dtype=torch.int32) if validate else None
+        call("nr_rays_from_pixels_intr_fwd", ptr(img), ptr(px), ptr(ps), ps.shape[0], H, W, ptr(fxy), B, ptr(ro),
+             ptr(rd), ptr(flag), _stream())
+        _raise_if_flagged(flag, ps.shape[0], "image index")
+        ctx.save_for_backward(img, px, ps, fxy)
+        ctx.args = (H, W)
+        return ro, rd
+
+    @staticmethod
+    def backward(ctx, g_ro, g_rd):
+        img, px, ps, fxy = ctx.saved_tensors
+        H, W = ctx.args
+        B = img.shape[0]
+        if g_ro is None:
+            g_ro = torch.zeros(B, 3, device=px.device, dtype=_f32)
+        g_poses = torch.zeros_like(ps)
+        g_fxy = torch.empty(2, device=px.device, dtype=_f32)  # written, not accumulated
+        n_img = ps.shape[0]
+        ws = torch.empty(int(_hip.load().nr_rays_from_pixels_intr_bwd_workspace_bytes(n_img)), device=px.device,
+                         dtype=torch.uint8)
+        call("nr_rays_from_pixels_intr_bwd", ptr(img), ptr(px), ptr(ps), n_img, H, W, ptr(fxy), B, ptr(_c(g_ro)),
+             ptr(_c(g_rd)), ptr(g_poses), ptr(g_fxy), ptr(ws), _stream())
+        return (None, None, g_poses if ctx.needs_input_grad[2] else None, None, None,
+                g_fxy if ctx.needs_input_grad[5] else None, None)
+
+
 def check_index_range(idx: torch.Tensor, limit: int, what: str = "index") -> None:
     """Raise IndexError (as torch indexing in the reference would) if any idx is outside
     [0, limit).  One device kernel plus one host read of the flag."""
@@ -479,8 +527,17 @@ def rays_from_pixels(img_idx, pix, poses, H, W, focal, validate: bool = False):
     """get_rays_from_pixels (data_pose_opt.py:83-148) in one pass; poses indexed by img_idx.
     ``validate`` raises IndexError for an img_idx outside [0, poses.shape[0]) (the
     kernel's validating mode: same launch, one host read of its flag); unchecked
-    out-of-range rays come out NaN and get no pose gradient."""
+    out-of-range rays come out NaN and get no pose gradient.
+    ``focal``: a Python number (both axes, no gradient), or a contiguous (2,) fp32 device
+    tensor (fx, fy) that the kernels read from device memory and that gets a gradient
+    (learned intrinsics; with fx == fy the same rays and pose gradients bit for bit)."""
     _check(img_idx, pix, poses)
+    if isinstance(focal, torch.Tensor):
+        _check(focal)
+        if focal.shape != (2,) or focal.dtype != _f32 or focal.device != poses.device or not focal.is_contiguous():
+            raise ValueError(f"rays_from_pixels: a tensor focal must be contiguous fp32 (fx, fy) on {poses.device}, "
+                             f"got {tuple(focal.shape)} {focal.dtype} on {focal.device}")
+        return _RaysFromPixelsIntr.apply(img_idx, pix, poses, H, W, focal, bool(validate))
     return _RaysFromPixels.apply(img_idx, pix, poses, H, W, focal, bool(validate))
 
 

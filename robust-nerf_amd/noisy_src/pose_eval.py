@@ -129,6 +129,30 @@ def aligned_pose_errors(pred_poses, gt_poses) -> Dict[str, object]:
     return out
 
 
+FOCAL_KEYS = ("initial_focal", "optimized_focal", "ground_truth_focal")
+
+
+def focal_errors(record) -> Dict[str, object]:
+    """The focal report of a ``final_poses.pt`` written with ``--learn_focal`` (the three
+    ``*_focal`` entries, (fx, fy) each): the values and their errors against the ground
+    truth in per cent, per axis and as the mean of the absolute values.  {} for a record
+    without the entries.  The Sim(3) alignment does not touch this number: a focal length
+    that is off by a factor is compensated by the cameras' distance to the scene, not by a
+    global scale of the frame."""
+    if not all(k in record for k in FOCAL_KEYS):
+        return {}
+    init, opt, gt = (torch.as_tensor(record[k], dtype=torch.float64).reshape(-1).expand(2) for k in FOCAL_KEYS)
+
+    def pct(f):
+        return ((f / gt - 1.0) * 100.0).tolist()
+
+    e0, e1 = pct(init), pct(opt)
+    return {"initial_focal": init.tolist(), "optimized_focal": opt.tolist(), "ground_truth_focal": gt.tolist(),
+            "initial_focal_error_pct": e0, "optimized_focal_error_pct": e1,
+            "initial_focal_error_pct_mean_abs": float(np.mean(np.abs(e0))),
+            "optimized_focal_error_pct_mean_abs": float(np.mean(np.abs(e1)))}
+
+
 def main(argv=None) -> None:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m noisy_src.pose_eval",
@@ -141,11 +165,17 @@ def main(argv=None) -> None:
     gt = _poses64(d["ground_truth_poses"])
     raw = _poses64(d["optimized_poses"])
     res["unaligned"] = pose_error_summary([pose_error(gt[i], raw[i]) for i in range(gt.shape[0])])
+    focal = focal_errors(d)
+    if focal:
+        res["focal"] = focal
     out = a.out if a.out is not None else a.final_poses.parent / "aligned_pose_errors.json"
     out.write_text(json.dumps(res, indent=2))
     print(f"aligned: rot {res['rotation_error_mean']:.4f} deg, trans {res['translation_error_mean']:.5f} "
           f"(raw frame: rot {res['unaligned']['rotation_error_mean']:.4f} deg, "
           f"trans {res['unaligned']['translation_error_mean']:.5f}); scale {res['sim3']['s']:.6f}; wrote {out}")
+    if focal:
+        print(f"focal error: {focal['initial_focal_error_pct_mean_abs']:.3f} % -> "
+              f"{focal['optimized_focal_error_pct_mean_abs']:.3f} % (mean |f / f_gt - 1| over fx, fy)")
 
 
 if __name__ == "__main__":

@@ -98,9 +98,14 @@ def train_step(renderer: NeRFRenderer, optimizer: torch.optim.Optimizer, batch: 
 
 @torch.no_grad()
 def render_image(renderer: NeRFRenderer, pose: torch.Tensor, H: int, W: int, focal: float,
-                 chunk_size: int = 1024 * 4) -> Dict[str, torch.Tensor]:
-    """Reference train.py:122-160: every pixel of one view, deterministic (is_train=False)."""
-    dirs = get_ray_directions(H, W, focal, device=pose.device)
+                 chunk_size: int = 1024 * 4, fxy=None) -> Dict[str, torch.Tensor]:
+    """Reference train.py:122-160: every pixel of one view, deterministic (is_train=False).
+    ``fxy`` (optional): focal lengths (fx, fy) learned with the poses, in place of ``focal``."""
+    if fxy is None:
+        dirs = get_ray_directions(H, W, focal, device=pose.device)
+    else:
+        from . import ops
+        dirs = ops.ray_directions_xy(H, W, fxy[0], fxy[1], W / 2.0, H / 2.0, pose.device)
     rays_o, rays_d = get_rays(dirs, pose.detach().contiguous())
     out = renderer(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), chunk_size=chunk_size, is_train=False)
     key = "fine" if "rgb_fine" in out else "coarse"

@@ -28,6 +28,11 @@ Joint NeRF + camera-pose training step — drop-in for ShawnnnLiu/Robust-NeRF
   iteration, folded into the MLP's weight images (``NeRF.set_pe_window``).  The reference
   lists it as future work; it is meant for ``fixed_small_angle=True``
   (``--fixed_small_angle``), where the rotation gradients are live.
+* ``learn_focal="shared" | "xy"`` (``--learn_focal``, with ``--focal_init_scale``) learns the
+  focal length with the poses as NeRF-- does (Wang et al. 2021; the reference's other
+  future-work item): ``CameraIntrinsics`` holds a log scale on the dataset's focal length,
+  the ray kernels read (fx, fy) from device memory (``nr_rays_from_pixels_intr_fwd/bwd``), so
+  the graphs follow it, and it shares the pose Adam, schedule and delay.
 """
 
 from __future__ import annotations
@@ -150,6 +155,51 @@ class CameraPoseParameters(nn.Module):
         }
 
 
+class CameraIntrinsics(nn.Module):
+    """A learnable focal length for joint optimisation with the poses (NeRF--, Wang et al.
+    2021; the reference's POSE_OPTIMIZATION.md lists it as future work).
+
+    One parameter ``log_scale``, zero-initialised: (1,) in mode "shared" (one factor for both
+    axes) or (2,) in mode "xy".  ``fxy()`` = ``focal_init * exp(log_scale)`` as a (2,) device
+    tensor (fx, fy) that the ray kernels read from device memory.  At zero it is
+    ``focal_init`` exactly, so the first step's rays are those of the fixed focal length.
+    The log makes one learning rate mean the same at every focal length: a step of 1e-4
+    changes it by 0.01 %.  ``focal_init``: a number, or a pair (fx, fy)."""
+
+    MODES = ("shared", "xy")
+
+    def __init__(self, focal_init, mode: str = "shared"):
+        super().__init__()
+        if mode not in self.MODES:
+            raise ValueError(f"CameraIntrinsics: mode must be one of {self.MODES}, not {mode!r}")
+        f = torch.as_tensor(focal_init, dtype=torch.float32).reshape(-1)
+        if f.numel() not in (1, 2) or not bool((f > 0).all()):
+            raise ValueError(f"CameraIntrinsics: focal_init must be one or two positive numbers, got {focal_init!r}")
+        self.mode = mode
+        self.register_buffer("focal_init", f.expand(2).clone())
+        self.log_scale = nn.Parameter(torch.zeros(1 if mode == "shared" else 2))
+
+    @classmethod
+    def from_state_dict(cls, state) -> "CameraIntrinsics":
+        """The module a checkpoint's ``intrinsics`` entry was saved from (on the CPU)."""
+        out = cls(state["focal_init"], "shared" if state["log_scale"].numel() == 1 else "xy")
+        out.load_state_dict(state)
+        return out
+
+    def fxy(self) -> torch.Tensor:
+        return self.focal_init * torch.exp(self.log_scale)
+
+    def fxy_values(self) -> Tuple[float, float]:
+        """(fx, fy) as Python floats (one host read; for renders and reports, not the step)."""
+        fx, fy = self.fxy().detach().cpu().tolist()
+        return fx, fy
+
+    def focal_error_pct(self, reference_focal: float) -> torch.Tensor:
+        """mean over the axes of |f / reference - 1| in per cent (a device scalar, no sync)."""
+        with torch.no_grad():
+            return (self.fxy() / float(reference_focal) - 1.0).abs().mean() * 100.0
+
+
 def train_step_with_poses(model_coarse: NeRF, model_fine: Optional[NeRF], camera_params: CameraPoseParameters,
                           pixel_sampler: PixelSampler, optimizer_nerf: torch.optim.Optimizer,
                           optimizer_poses: Optional[torch.optim.Optimizer], pixel_batch: PixelBatch,
@@ -212,9 +262,14 @@ def train_step_with_poses(model_coarse: NeRF, model_fine: Optional[NeRF], camera
 
 @torch.no_grad()
 def render_image_with_pose(model_coarse: NeRF, model_fine: Optional[NeRF], pose: torch.Tensor, H: int, W: int,
-                           focal: float, render_config: RenderConfig, chunk_size: int = 1024 * 4) -> Dict[str, torch.Tensor]:
-    """Reference train_pose_opt.py:415-470."""
-    dirs = get_ray_directions(H, W, focal, device=pose.device)
+                           focal: float, render_config: RenderConfig, chunk_size: int = 1024 * 4,
+                           fxy: Optional[Tuple[float, float]] = None) -> Dict[str, torch.Tensor]:
+    """Reference train_pose_opt.py:415-470.  ``fxy`` (optional): learned focal lengths
+    (fx, fy) in place of ``focal`` (``ops.ray_directions_xy``)."""
+    if fxy is None:
+        dirs = get_ray_directions(H, W, focal, device=pose.device)
+    else:
+        dirs = ops.ray_directions_xy(H, W, fxy[0], fxy[1], W / 2.0, H / 2.0, pose.device)
     rays_o, rays_d = get_rays(dirs, pose.contiguous())
     rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
     key = "fine" if (model_fine is not None and render_config.use_hierarchical) else "coarse"
@@ -238,16 +293,17 @@ def _window_dict(net: NeRF) -> Optional[Dict[str, Optional[List[float]]]]:
 def evaluate_with_poses(model_coarse: NeRF, model_fine: Optional[NeRF], camera_params: CameraPoseParameters,
                         val_data: BlenderData, val_indices: torch.Tensor, render_config: RenderConfig,
                         logger: Optional[ExperimentLogger] = None, iteration: int = 0, num_images: int = 5,
-                        lpips_metric=None) -> ValidationMetrics:
+                        lpips_metric=None, fxy: Optional[Tuple[float, float]] = None) -> ValidationMetrics:
     """Reference train_pose_opt.py:474-545: renders the first ``num_images`` validation
     views from their GROUND-TRUTH poses (the learnable poses are the training views');
     PNGs of the first three when a logger is given.  The networks render with their
-    current positional-encoding windows (``NeRF.set_pe_window``)."""
+    current positional-encoding windows (``NeRF.set_pe_window``), and with the learned
+    focal lengths ``fxy`` when given (the field was fitted to rays of that focal length)."""
     psnr, ssim, mse, lp = [], [], [], []
     for i, idx in enumerate(val_indices[:min(num_images, len(val_indices))]):
         idx = int(idx)
         out = render_image_with_pose(model_coarse, model_fine, val_data.poses[idx], val_data.H, val_data.W,
-                                     val_data.focal, render_config)
+                                     val_data.focal, render_config, fxy=fxy)
         pred, target = out["rgb"], val_data.images[idx]
         mse.append(compute_mse(pred, target).item())
         psnr.append(compute_psnr(pred, target).item())
@@ -266,9 +322,10 @@ def evaluate_with_poses(model_coarse: NeRF, model_fine: Optional[NeRF], camera_p
 def save_checkpoint_with_poses(output_dir, iteration: int, model_coarse, model_fine, camera_params,
                                optimizer_nerf, optimizer_poses, config: NeRFConfig, noise_config=None,
                                metrics: Optional[Dict] = None, pose_errors: Optional[Dict] = None,
-                               is_best: bool = False) -> None:
+                               is_best: bool = False, intrinsics: Optional[CameraIntrinsics] = None) -> None:
     """Reference train_pose_opt.py:548-610: the train.py checkpoint plus ``camera_params``,
-    ``optimizer_nerf`` / ``optimizer_poses``, ``initial_poses`` and ``pose_errors``."""
+    ``optimizer_nerf`` / ``optimizer_poses``, ``initial_poses`` and ``pose_errors``; with
+    learned ``intrinsics`` also their state dict as ``intrinsics``."""
     from .train import checkpoint_config, noise_dict
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
@@ -279,6 +336,8 @@ def save_checkpoint_with_poses(output_dir, iteration: int, model_coarse, model_f
     window = _window_dict(model_coarse)
     if window is not None:
         ckpt["mi355x"]["pe_window"] = window  # both networks share the schedule
+    if intrinsics is not None:
+        ckpt["intrinsics"] = intrinsics.state_dict()  # CameraIntrinsics.from_state_dict rebuilds it
     if model_fine is not None:
         ckpt["model_fine"] = model_fine.state_dict()
     if optimizer_poses is not None:
@@ -309,7 +368,8 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                  train_data: Optional[BlenderData] = None, val_data: Optional[BlenderData] = None,
                                  process_group=None, experiment_name: Optional[str] = None,
                                  log=print, graph: bool = False, c2f: Optional[Tuple[float, float]] = None,
-                                 fixed_small_angle: bool = False) -> Dict[str, object]:
+                                 fixed_small_angle: bool = False, learn_focal: Optional[str] = None,
+                                 focal_init_scale: float = 1.0) -> Dict[str, object]:
     """Reference train_pose_opt.py:613-1054 (same arguments, outputs and files).
     ``train_data`` / ``val_data`` (optional) replace the on-disk scene; ``process_group``
     makes it data parallel; ``experiment_name`` pins the generated run name (all ranks).
@@ -321,7 +381,13 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     ``c2f=(start, end)`` windows both positional encodings coarse to fine over that
     fraction of the run (``c2f_alpha``, ``pe_window_weights``); ``fixed_small_angle`` is
     ``CameraPoseParameters``' (live rotation gradients at w = 0).  Neither is in the
-    reference; both default to its behaviour."""
+    reference; both default to its behaviour.
+    ``learn_focal`` ("shared" or "xy"; ``--learn_focal``) learns the focal length with the
+    poses (``CameraIntrinsics``, NeRF--), starting from ``focal_init_scale`` times the
+    dataset's: same Adam, learning rate, schedule and delay as the poses; validation renders
+    use the learned value, the log and train_metrics.csv report its error in per cent
+    against the dataset's, checkpoints gain ``intrinsics`` and final_poses.pt the three
+    ``*_focal`` entries.  None (the default) is the reference's fixed focal length."""
     import torch.distributed as dist
 
     rank, world = 0, 1
@@ -366,6 +432,12 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         initial_poses = gt_train_poses.clone()
     camera_params = CameraPoseParameters(initial_poses, learn_rotation, learn_translation,
                                          fixed_small_angle=fixed_small_angle).to(device)
+    intrinsics = None
+    if learn_focal is not None:
+        if not focal_init_scale > 0:
+            raise ValueError(f"focal_init_scale must be positive, got {focal_init_scale}")
+        intrinsics = CameraIntrinsics(train_data.focal * focal_init_scale, learn_focal).to(device)
+    gt_focal = float(train_data.focal)
     model_coarse, model_fine = create_nerf_for(config, device)
     if logger is not None:
         logger.log_model_info(model_coarse, "model_coarse")
@@ -376,7 +448,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     trainer = PoseTrainer(model_coarse, model_fine, camera_params, pixel_sampler, config.render, lr=config.train.lr,
                           pose_lr=pose_lr, lr_decay=config.train.lr_decay, rotation_reg_weight=rotation_reg_weight,
                           translation_reg_weight=translation_reg_weight, process_group=process_group,
-                          pe_schedule=pe_schedule)
+                          pe_schedule=pe_schedule, intrinsics=intrinsics)
     optimizer_nerf, optimizer_poses = trainer.optimizer_nerf, trainer.optimizer_poses
     lpips_metric = LPIPSMetric(device=device) if rank == 0 else None
     if lpips_metric is not None and not lpips_metric.available:
@@ -388,6 +460,8 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
             extra["c2f"] = list(c2f)
         if fixed_small_angle:
             extra["fixed_small_angle"] = True
+        if intrinsics is not None:
+            extra["learn_focal"] = {"mode": learn_focal, "focal_init_scale": focal_init_scale}
         (output_dir / "experiment_config.json").write_text(json.dumps({
             "scene": config.data.scene_name, "experiment_name": exp_name, "init_mode": init_mode,
             "pose_optimization": {"learn_rotation": learn_rotation, "learn_translation": learn_translation,
@@ -419,11 +493,16 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         psnr = -10.0 * math.log10(last) if last > 0 else float("inf")
         logger.log_training(TrainingMetrics(iteration=it, loss=vm["loss"], loss_coarse=vm["loss_coarse"],
                                             loss_fine=vm.get("loss_fine"), psnr=psnr, learning_rate=lr,
-                                            time_per_iter=batch_time, rays_per_sec=B / batch_time))
+                                            time_per_iter=batch_time, rays_per_sec=B / batch_time,
+                                            focal_error_pct=vm.get("focal_error_pct")))
         if it % config.train.log_every == 0:
+            focal = f" | focal err: {vm['focal_error_pct']:.3f}%" if "focal_error_pct" in vm else ""
             log(f"[{it:7d}/{config.train.num_iterations}] loss: {vm['loss']:.5f} | psnr: {psnr:.2f} | "
-                f"lr: {lr:.2e} | poses: {'optimizing' if now else 'frozen'} | "
+                f"lr: {lr:.2e} | poses: {'optimizing' if now else 'frozen'}{focal} | "
                 f"time: {(time.time() - start) / 60:.1f}min")
+
+    def learned_fxy():
+        return intrinsics.fxy_values() if intrinsics is not None else None
 
     for iteration in range(config.train.num_iterations):
         # the global batch, identical on every rank (one process in graph mode: the gather
@@ -443,8 +522,12 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         else:
             m = trainer.step(*args, iteration=iteration)
         keys = ["loss", "loss_coarse"] + (["loss_fine"] if "loss_fine" in m else [])
+        vals = [m[k] for k in keys]
+        if intrinsics is not None:  # a device scalar like the losses: read one iteration late
+            keys.append("focal_error_pct")
+            vals.append(intrinsics.focal_error_pct(gt_focal))
         t_now = time.time()
-        log_iteration(lagged.push(mean_over_ranks([m[k] for k in keys], process_group),
+        log_iteration(lagged.push(mean_over_ranks(vals, process_group),
                                   (iteration, keys, optimizer_nerf.param_groups[0]["lr"], now, t_now - t_prev)))
         t_prev = t_now
         if logger is None:
@@ -454,21 +537,24 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         if iteration % config.train.val_every == 0 and iteration > 0:
             pe = camera_params.compute_pose_errors(gt_train_poses)
             vmx = evaluate_with_poses(model_coarse, model_fine, camera_params, val_data, val_idx, rc, logger,
-                                      iteration, num_images=5, lpips_metric=lpips_metric)
+                                      iteration, num_images=5, lpips_metric=lpips_metric, fxy=learned_fxy())
             logger.log_validation(vmx)
             is_best = vmx.psnr > best_psnr
             best_psnr = max(best_psnr, vmx.psnr)
+            focal = (f"; focal error {float(intrinsics.focal_error_pct(gt_focal)):.3f} %"
+                     if intrinsics is not None else "")
             log(f"  validation @ {iteration}: PSNR {vmx.psnr:.2f} dB; pose error rot "
-                f"{pe['rotation_error_mean']:.3f} deg, trans {pe['translation_error_mean']:.4f}")
+                f"{pe['rotation_error_mean']:.3f} deg, trans {pe['translation_error_mean']:.4f}{focal}")
             save_checkpoint_with_poses(output_dir, iteration, model_coarse, model_fine, camera_params,
                                        optimizer_nerf, optimizer_poses, config, noise_config,
                                        metrics={"psnr": vmx.psnr, "ssim": vmx.ssim}, pose_errors=pe,
-                                       is_best=is_best)
+                                       is_best=is_best, intrinsics=intrinsics)
             t_prev = time.time()  # the next iteration's time excludes the validation
         elif iteration % config.train.save_every == 0 and iteration > 0:
             pe = camera_params.compute_pose_errors(gt_train_poses)
             save_checkpoint_with_poses(output_dir, iteration, model_coarse, model_fine, camera_params,
-                                       optimizer_nerf, optimizer_poses, config, noise_config, pose_errors=pe)
+                                       optimizer_nerf, optimizer_poses, config, noise_config, pose_errors=pe,
+                                       intrinsics=intrinsics)
             t_prev = time.time()
     log_iteration(lagged.flush())
     if pe_schedule is not None:
@@ -476,24 +562,33 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         trainer.set_pe_windows(config.train.num_iterations)
     result = {"model_coarse": model_coarse, "model_fine": model_fine, "camera_params": camera_params,
               "output_dir": output_dir, "pose_errors": camera_params.compute_pose_errors(gt_train_poses)}
+    if intrinsics is not None:
+        result["intrinsics"] = intrinsics
+        result["focal_error_pct"] = float(intrinsics.focal_error_pct(gt_focal))
     if logger is not None:
         final_pe = result["pose_errors"]
         final = evaluate_with_poses(model_coarse, model_fine, camera_params, val_data, val_idx, rc, logger,
                                     config.train.num_iterations, num_images=val_data.images.shape[0],
-                                    lpips_metric=lpips_metric)
+                                    lpips_metric=lpips_metric, fxy=learned_fxy())
         # (the reference does not write the final evaluation to val_metrics.csv, :1002-1019)
         save_checkpoint_with_poses(output_dir, config.train.num_iterations, model_coarse, model_fine, camera_params,
                                    optimizer_nerf, optimizer_poses, config, noise_config,
-                                   metrics={"psnr": final.psnr, "ssim": final.ssim}, pose_errors=final_pe)
+                                   metrics={"psnr": final.psnr, "ssim": final.ssim}, pose_errors=final_pe,
+                                   intrinsics=intrinsics)
         with torch.no_grad():
             final_poses = camera_params.get_all_poses()
-        torch.save({"initial_poses": camera_params.initial_poses.cpu(), "optimized_poses": final_poses.cpu(),
-                    "ground_truth_poses": gt_train_poses.cpu(), "pose_errors": final_pe},
-                   output_dir / "final_poses.pt")
+        record = {"initial_poses": camera_params.initial_poses.cpu(), "optimized_poses": final_poses.cpu(),
+                  "ground_truth_poses": gt_train_poses.cpu(), "pose_errors": final_pe}
+        if intrinsics is not None:  # (fx, fy) each, for pose_eval's focal report
+            record.update(initial_focal=intrinsics.focal_init.detach().cpu().clone(),
+                          optimized_focal=intrinsics.fxy().detach().cpu(),
+                          ground_truth_focal=torch.full((2,), gt_focal, dtype=torch.float32))
+        torch.save(record, output_dir / "final_poses.pt")
         logger.save_summary()
         logger.close()
+        focal = f", focal error {result['focal_error_pct']:.3f} %" if intrinsics is not None else ""
         log(f"final: PSNR {final.psnr:.2f} dB; pose error rot {final_pe['rotation_error_mean']:.3f} deg, "
-            f"trans {final_pe['translation_error_mean']:.4f}; results in {output_dir}")
+            f"trans {final_pe['translation_error_mean']:.4f}{focal}; results in {output_dir}")
         result["val"] = final
     if process_group is not None:
         dist.barrier(process_group)
@@ -519,7 +614,7 @@ GRAPH_HELP = ("replay the joint step from hipGraphs, one for frozen poses and on
 
 def build_arg_parser():
     """Reference train_pose_opt.py:1057-1142 flags (same names and defaults) plus ``--precision``,
-    ``--graph``, ``--c2f`` and ``--fixed_small_angle``."""
+    ``--graph``, ``--c2f``, ``--fixed_small_angle``, ``--learn_focal`` and ``--focal_init_scale``."""
     import argparse
     ap = argparse.ArgumentParser(description="Joint NeRF + camera pose optimisation (MI355X HIP path)")
     ap.add_argument("--scene", type=str, default="lego")
@@ -557,6 +652,12 @@ def build_arg_parser():
     ap.add_argument("--fixed_small_angle", action="store_true",
                     help="exact Rodrigues derivative at zero rotation deltas, so the rotations learn (the "
                          "reference blocks that gradient)")
+    ap.add_argument("--learn_focal", type=str, default=None, choices=list(CameraIntrinsics.MODES),
+                    help="learn the focal length jointly with the poses (NeRF--): one factor for both axes "
+                         "(shared) or one per axis (xy), with the pose learning rate, schedule and delay")
+    ap.add_argument("--focal_init_scale", type=float, default=1.0,
+                    help="with --learn_focal: start from this multiple of the dataset's focal length (the "
+                         "deterministic counterpart of the pose-noise flags)")
     return ap
 
 
@@ -586,13 +687,14 @@ def main(argv=None) -> None:
                                  not a.no_learn_rotation, not a.no_learn_translation, a.rotation_reg_weight,
                                  a.translation_reg_weight, process_group=pg, experiment_name=name[0],
                                  graph=a.graph, c2f=tuple(a.c2f) if a.c2f is not None else None,
-                                 fixed_small_angle=a.fixed_small_angle)
+                                 fixed_small_angle=a.fixed_small_angle, learn_focal=a.learn_focal,
+                                 focal_init_scale=a.focal_init_scale)
     if pg is not None:
         import torch.distributed as dist
         dist.destroy_process_group()
 
 
-__all__ = ["set_seed", "CameraPoseParameters", "train_step_with_poses", "render_image_with_pose",
+__all__ = ["set_seed", "CameraPoseParameters", "CameraIntrinsics", "train_step_with_poses", "render_image_with_pose",
            "evaluate_with_poses", "save_checkpoint_with_poses", "generate_experiment_name",
            "train_with_pose_optimization", "pe_window_weights", "c2f_alpha", "main"]
 
