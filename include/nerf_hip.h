@@ -91,28 +91,31 @@ int nr_rays_from_pixels_bwd(const int64_t* img_idx, const float* pix,
                             nr_stream_t stream);
 /* ---- A1 / A3 with learned intrinsics (no reference counterpart; its
  *          POSE_OPTIMIZATION.md lists focal-length optimisation as future work)
- * nr_ray_directions with a focal length per axis:
- * dirs (H,W,3) = ((i-cx)/fx, -(j-cy)/fy, -1).                                */
+ * nr_ray_directions with a focal length per axis (the same kernel; it passes
+ * focal twice): dirs (H,W,3) = ((i-cx)/fx, -(j-cy)/fy, -1).                 */
 int nr_ray_directions_xy(int H, int W, float fx, float fy, float cx, float cy,
                          float* dirs, nr_stream_t stream);
 /* nr_rays_from_pixels_fwd with fxy = {fx, fy}, two floats in DEVICE memory
  * read when the kernel runs (a captured graph sees the current value):
- * dx = (u - W/2)/fx, dy = -((v - H/2)/fy).  With fx == fy == focal the rays
- * are those of nr_rays_from_pixels_fwd bit for bit; out-of-range img_idx and
- * bad_index behave as there.                                                 */
+ * dx = (u - W/2)/fx, dy = -((v - H/2)/fy).  Both entries run one kernel body
+ * (the focal pair an argument there, a load here), so with fx == fy == focal
+ * the rays are those of nr_rays_from_pixels_fwd bit for bit; out-of-range
+ * img_idx and bad_index behave as there.  An empty batch (B == 0) may come
+ * with null arrays here, not there.                                          */
 int nr_rays_from_pixels_intr_fwd(const int64_t* img_idx, const float* pix,
                                  const float* poses, int n_img, int H, int W,
                                  const float* fxy, int B, float* rays_o,
                                  float* rays_d, int* bad_index,
                                  nr_stream_t stream);
-/* Backward of the above.  g_poses exactly as nr_rays_from_pixels_bwd
- * (ACCUMULATED, caller zeroes; the same bits when fx == fy).  g_fxy (2 floats)
- * is WRITTEN: dL/dfx, dL/dfy summed over the batch, 0 when g_rays_d is NULL or
- * B == 0.  Each image's workgroup carries the two sums through its fixed tree
- * into workspace ((n_img,2) floats, nr_..._workspace_bytes(n_img), fully
- * overwritten); a second one-workgroup launch adds them over the images in a
- * fixed order.  No atomics; rays with an out-of-range img_idx contribute
- * nothing.                                                                   */
+/* Backward of the above: the kernel body of nr_rays_from_pixels_bwd with two
+ * more rows in its reduction.  g_poses exactly as there (ACCUMULATED, caller
+ * zeroes; each row is reduced on its own, so the same bits when fx == fy).
+ * g_fxy (2 floats) is WRITTEN: dL/dfx, dL/dfy summed over the batch, 0 when
+ * g_rays_d is NULL or B == 0.  Each image's workgroup carries the two sums
+ * through its fixed tree into workspace ((n_img,2) floats,
+ * nr_..._workspace_bytes(n_img), fully overwritten); a second one-workgroup
+ * launch, made for an empty batch too, adds them over the images in a fixed
+ * order.  No atomics; rays with an out-of-range img_idx contribute nothing.  */
 int64_t nr_rays_from_pixels_intr_bwd_workspace_bytes(int n_img);
 int nr_rays_from_pixels_intr_bwd(const int64_t* img_idx, const float* pix,
                                  const float* poses, int n_img, int H, int W,
@@ -189,7 +192,8 @@ int nr_positional_encoding_bwd(const float* x, int64_t M, int C, int num_freqs,
 /* The windowed encoding (no reference counterpart; additive to ABI 5): frequency
  * k's sin and cos columns times w[k]; the raw input columns are not weighted.
  * w: num_freqs floats in DEVICE memory, read by the kernel (capturable; a replay
- * sees the values of its time), nullable = all ones.                          */
+ * sees the values of its time), nullable = all ones: the plain entry points
+ * above launch these kernels with w null, so the two agree bit for bit.      */
 int nr_positional_encoding_windowed(const float* x, int64_t M, int C,
                                     int num_freqs, int include_input,
                                     int log_sampling, const float* w,

@@ -276,32 +276,9 @@ def expand_viewdirs(rays_d: torch.Tensor, S: int) -> torch.Tensor:
 
 # ---------------------------------------------------------------- A6 ---------
 class _PosEnc(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, L, include_input, log_sampling):
-        xc = _c(x)
-        C = xc.shape[-1]
-        M = xc.numel() // C
-        D = (1 if include_input else 0) + 2 * L
-        out = torch.empty(*xc.shape[:-1], C * D, device=xc.device, dtype=_f32)
-        call("nr_positional_encoding", ptr(xc), M, C, L, int(include_input), int(log_sampling), ptr(out), _stream())
-        ctx.save_for_backward(xc)
-        ctx.args = (L, include_input, log_sampling)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        (xc,) = ctx.saved_tensors
-        L, inc, logs = ctx.args
-        C = xc.shape[-1]
-        gx = torch.empty_like(xc)
-        call("nr_positional_encoding_bwd", ptr(xc), xc.numel() // C, C, L, int(inc), int(logs), ptr(_c(g)), ptr(gx),
-             _stream())
-        return gx, None, None, None
-
-
-class _PosEncWindowed(torch.autograd.Function):
-    """The encoding with a per-frequency weight read from device memory (``window``: L
-    floats; its values at the time each kernel runs, so it may be rewritten in place)."""
+    """``window`` None: the plain entry points.  A tensor: the windowed ones, a per-frequency
+    weight read from device memory (L floats; their values at the time each kernel runs, so
+    it may be rewritten in place)."""
 
     @staticmethod
     def forward(ctx, x, L, include_input, log_sampling, window):
@@ -310,20 +287,25 @@ class _PosEncWindowed(torch.autograd.Function):
         M = xc.numel() // C
         D = (1 if include_input else 0) + 2 * L
         out = torch.empty(*xc.shape[:-1], C * D, device=xc.device, dtype=_f32)
-        call("nr_positional_encoding_windowed", ptr(xc), M, C, L, int(include_input), int(log_sampling), ptr(window),
-             ptr(out), _stream())
+        ctx.args = (L, int(include_input), int(log_sampling))
+        if window is None:
+            call("nr_positional_encoding", ptr(xc), M, C, *ctx.args, ptr(out), _stream())
+        else:
+            call("nr_positional_encoding_windowed", ptr(xc), M, C, *ctx.args, ptr(window), ptr(out), _stream())
         ctx.save_for_backward(xc, window)
-        ctx.args = (L, include_input, log_sampling)
         return out
 
     @staticmethod
     def backward(ctx, g):
         xc, window = ctx.saved_tensors
-        L, inc, logs = ctx.args
         C = xc.shape[-1]
+        M = xc.numel() // C
         gx = torch.empty_like(xc)
-        call("nr_positional_encoding_windowed_bwd", ptr(xc), xc.numel() // C, C, L, int(inc), int(logs), ptr(window),
-             ptr(_c(g)), ptr(gx), _stream())
+        if window is None:
+            call("nr_positional_encoding_bwd", ptr(xc), M, C, *ctx.args, ptr(_c(g)), ptr(gx), _stream())
+        else:
+            call("nr_positional_encoding_windowed_bwd", ptr(xc), M, C, *ctx.args, ptr(window), ptr(_c(g)), ptr(gx),
+                 _stream())
         return gx, None, None, None, None
 
 
@@ -331,11 +313,11 @@ def positional_encoding(x, num_freqs, include_input=True, log_sampling=True, win
     """``window`` (optional, (num_freqs,) fp32 on x's device): a weight per frequency on
     its sin / cos columns (coarse-to-fine registration); it gets no gradient."""
     _check(x)
-    if window is None:
-        return _PosEnc.apply(x, num_freqs, include_input, log_sampling)
-    if window.dtype != _f32 or window.numel() != num_freqs or window.device != x.device:
-        raise ValueError(f"positional_encoding: window must be {num_freqs} fp32 weights on {x.device}")
-    return _PosEncWindowed.apply(x, num_freqs, include_input, log_sampling, window.detach())
+    if window is not None:
+        if window.dtype != _f32 or window.numel() != num_freqs or window.device != x.device:
+            raise ValueError(f"positional_encoding: window must be {num_freqs} fp32 weights on {x.device}")
+        window = window.detach()
+    return _PosEnc.apply(x, num_freqs, include_input, log_sampling, window)
 
 
 # ---------------------------------------------------------------- A8 ---------
@@ -446,6 +428,11 @@ def composite_mse(rgb, sigma, z_vals, rays_d, target, noise=None, white_backgrou
 
 # ---------------------------------------------------------------- A3 / A4 ----
 class _RaysFromPixels(torch.autograd.Function):
+    """``focal``: a Python number, a kernel argument; or the focal lengths (fx, fy) in device
+    memory, read when the kernels run (so a captured graph follows a focal length that changes
+    every step), with a gradient for them beside the poses'.  Which of the two only picks the
+    entry point."""
+
     @staticmethod
     def forward(ctx, img_idx, pix, poses, H, W, focal, validate):
         img = img_idx.to(torch.int64).contiguous()
@@ -454,60 +441,34 @@ class _RaysFromPixels(torch.autograd.Function):
         ro = torch.empty(B, 3, device=px.device, dtype=_f32)
         rd = torch.empty(B, 3, device=px.device, dtype=_f32)
         flag = torch.zeros(1, device=px.device, dtype=torch.int32) if validate else None
-        call("nr_rays_from_pixels_fwd", ptr(img), ptr(px), ptr(ps), ps.shape[0], H, W, float(focal), B, ptr(ro),
-             ptr(rd), ptr(flag), _stream())
-        _raise_if_flagged(flag, ps.shape[0], "image index")
-        ctx.save_for_backward(img, px, ps)
-        ctx.args = (H, W, float(focal))
-        return ro, rd
-
-    @staticmethod
-    def backward(ctx, g_ro, g_rd):
-        img, px, ps = ctx.saved_tensors
-        H, W, focal = ctx.args
-        B = img.shape[0]
-        if g_ro is None:
-            g_ro = torch.zeros(B, 3, device=px.device, dtype=_f32)
-        g_poses = torch.zeros_like(ps)
-        call("nr_rays_from_pixels_bwd", ptr(img), ptr(px), ptr(ps), ps.shape[0], H, W, focal, B, ptr(_c(g_ro)),
-             ptr(_c(g_rd)), ptr(g_poses), _stream())
-        return None, None, g_poses, None, None, None, None
-
-
-class _RaysFromPixelsIntr(torch.autograd.Function):
-    """``_RaysFromPixels`` with the focal lengths ``fxy`` = (fx, fy) in device memory, read
-    when the kernels run (so a captured graph follows a focal length that changes every
-    step), and with a gradient for them beside the poses'."""
-
-    @staticmethod
-    def forward(ctx, img_idx, pix, poses, H, W, fxy, validate):
-        img = img_idx.to(torch.int64).contiguous()
-        px, ps = _c(pix), _c(poses)
-        B = img.shape[0]
-        ro = torch.empty(B, 3, device=px.device, dtype=_f32)
-        rd = torch.empty(B, 3, device=px.device, dtype=_f32)
-        flag = torch.zeros(1, device=px.device, dtype=torch.int32) if validate else None
-        call("nr_rays_from_pixels_intr_fwd", ptr(img), ptr(px), ptr(ps), ps.shape[0], H, W, ptr(fxy), B, ptr(ro),
-             ptr(rd), ptr(flag), _stream())
+        if isinstance(focal, torch.Tensor):
+            entry, fxy, focal = "nr_rays_from_pixels_intr_fwd", focal, ptr(focal)
+        else:
+            entry, fxy, focal = "nr_rays_from_pixels_fwd", None, float(focal)
+        call(entry, ptr(img), ptr(px), ptr(ps), ps.shape[0], H, W, focal, B, ptr(ro), ptr(rd), ptr(flag), _stream())
         _raise_if_flagged(flag, ps.shape[0], "image index")
         ctx.save_for_backward(img, px, ps, fxy)
-        ctx.args = (H, W)
+        ctx.args = (H, W, focal)  # the number; with fxy unused
         return ro, rd
 
     @staticmethod
     def backward(ctx, g_ro, g_rd):
         img, px, ps, fxy = ctx.saved_tensors
-        H, W = ctx.args
-        B = img.shape[0]
+        H, W, focal = ctx.args
+        B, n_img = img.shape[0], ps.shape[0]
         if g_ro is None:
             g_ro = torch.zeros(B, 3, device=px.device, dtype=_f32)
         g_poses = torch.zeros_like(ps)
-        g_fxy = torch.empty(2, device=px.device, dtype=_f32)  # written, not accumulated
-        n_img = ps.shape[0]
-        ws = torch.empty(int(_hip.load().nr_rays_from_pixels_intr_bwd_workspace_bytes(n_img)), device=px.device,
-                         dtype=torch.uint8)
-        call("nr_rays_from_pixels_intr_bwd", ptr(img), ptr(px), ptr(ps), n_img, H, W, ptr(fxy), B, ptr(_c(g_ro)),
-             ptr(_c(g_rd)), ptr(g_poses), ptr(g_fxy), ptr(ws), _stream())
+        g_fxy = None
+        if fxy is None:
+            call("nr_rays_from_pixels_bwd", ptr(img), ptr(px), ptr(ps), n_img, H, W, focal, B, ptr(_c(g_ro)),
+                 ptr(_c(g_rd)), ptr(g_poses), _stream())
+        else:
+            g_fxy = torch.empty(2, device=px.device, dtype=_f32)  # written, not accumulated
+            ws = torch.empty(int(_hip.load().nr_rays_from_pixels_intr_bwd_workspace_bytes(n_img)), device=px.device,
+                             dtype=torch.uint8)
+            call("nr_rays_from_pixels_intr_bwd", ptr(img), ptr(px), ptr(ps), n_img, H, W, ptr(fxy), B, ptr(_c(g_ro)),
+                 ptr(_c(g_rd)), ptr(g_poses), ptr(g_fxy), ptr(ws), _stream())
         return (None, None, g_poses if ctx.needs_input_grad[2] else None, None, None,
                 g_fxy if ctx.needs_input_grad[5] else None, None)
 
@@ -519,8 +480,7 @@ def check_index_range(idx: torch.Tensor, limit: int, what: str = "index") -> Non
     i = idx.to(torch.int64).contiguous()
     flag = torch.zeros(1, device=i.device, dtype=torch.int32)
     call("nr_check_index_range", ptr(i), i.numel(), int(limit), ptr(flag), _stream())
-    if int(flag.item()):
-        raise IndexError(f"{what} out of range for {limit} entries")
+    _raise_if_flagged(flag, limit, what)
 
 
 def rays_from_pixels(img_idx, pix, poses, H, W, focal, validate: bool = False):
@@ -537,7 +497,6 @@ def rays_from_pixels(img_idx, pix, poses, H, W, focal, validate: bool = False):
         if focal.shape != (2,) or focal.dtype != _f32 or focal.device != poses.device or not focal.is_contiguous():
             raise ValueError(f"rays_from_pixels: a tensor focal must be contiguous fp32 (fx, fy) on {poses.device}, "
                              f"got {tuple(focal.shape)} {focal.dtype} on {focal.device}")
-        return _RaysFromPixelsIntr.apply(img_idx, pix, poses, H, W, focal, bool(validate))
     return _RaysFromPixels.apply(img_idx, pix, poses, H, W, focal, bool(validate))
 
 

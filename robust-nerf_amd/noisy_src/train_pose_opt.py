@@ -61,8 +61,8 @@ from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim
 from .model import NeRF
 from .noise import NoiseConfig, add_noise_to_poses, compute_pose_error
 from .optim import FusedAdam, clip_grad_norm_
-from .rays import get_ray_directions, get_rays
-from .rendering import render_rays
+from .rendering import NeRFRenderer, render_rays
+from .train import render_image
 
 
 def set_seed(seed: int) -> None:
@@ -266,22 +266,7 @@ def render_image_with_pose(model_coarse: NeRF, model_fine: Optional[NeRF], pose:
                            fxy: Optional[Tuple[float, float]] = None) -> Dict[str, torch.Tensor]:
     """Reference train_pose_opt.py:415-470.  ``fxy`` (optional): learned focal lengths
     (fx, fy) in place of ``focal`` (``ops.ray_directions_xy``)."""
-    if fxy is None:
-        dirs = get_ray_directions(H, W, focal, device=pose.device)
-    else:
-        dirs = ops.ray_directions_xy(H, W, fxy[0], fxy[1], W / 2.0, H / 2.0, pose.device)
-    rays_o, rays_d = get_rays(dirs, pose.contiguous())
-    rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
-    key = "fine" if (model_fine is not None and render_config.use_hierarchical) else "coarse"
-    rgb, depth, acc = [], [], []
-    for i in range(0, rays_o.shape[0], chunk_size):
-        o = render_rays(model_coarse, model_fine, rays_o[i:i + chunk_size], rays_d[i:i + chunk_size], render_config,
-                        is_train=False)
-        rgb.append(o[f"rgb_{key}"])
-        depth.append(o[f"depth_{key}"])
-        acc.append(o[f"acc_{key}"])
-    return {"rgb": torch.cat(rgb).reshape(H, W, 3), "depth": torch.cat(depth).reshape(H, W),
-            "acc": torch.cat(acc).reshape(H, W)}
+    return render_image(NeRFRenderer(model_coarse, model_fine, render_config), pose, H, W, focal, chunk_size, fxy)
 
 
 def _window_dict(net: NeRF) -> Optional[Dict[str, Optional[List[float]]]]:
