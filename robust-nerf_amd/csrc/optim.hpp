@@ -39,10 +39,12 @@ __device__ __forceinline__ float wave_sum_fixed(const float* __restrict__ x) {
     return ((r[0] + r[1]) + r[2]) + r[3];
 }
 
-// clip_grad_norm_ coefficient from a squared norm (train.py:115)
+// clip_grad_norm_ coefficient from a squared norm (train.py:115).  A NaN norm gives a NaN
+// coefficient, as torch.clamp(nan, max=1) does: the whole clip group turns NaN instead of
+// being updated unclipped.  Every other c selects what `c < 1 ? c : 1` selects.
 __device__ __forceinline__ float clip_coef(float sumsq, float max_norm) {
     const float c = max_norm / (sqrtf(sumsq) + 1e-6f);
-    return c < 1.0f ? c : 1.0f;
+    return !(c >= 1.0f) ? c : 1.0f;
 }
 
 // torch.optim.Adam (train.py:402) on one element, the grad first scaled by the clip

@@ -108,16 +108,43 @@ class FusedAdam(torch.optim.Optimizer):
         self._nerf_plans = {}
 
     def load_state_dict(self, state_dict) -> None:
-        """torch's load, then drop the flat m/v buffers so the next step adopts the loaded
-        exp_avg / exp_avg_sq (instead of updating stale buffers)."""
+        """torch's load, then own the loaded tensors (clones) and drop the flat m/v buffers,
+        so the next step adopts the loaded exp_avg / exp_avg_sq (instead of updating stale
+        buffers) and counts on step tensors nobody else holds."""
         super().load_state_dict(state_dict)
         self._flat_state.clear()
+        # torch hands tensors of the right dtype and device over as they are.  Own them: a
+        # counter or a moment that the saved dict shares (with another parameter, or with
+        # the live optimizer it came from) would be advanced by every holder
+        for st in self.state.values():
+            for k, t in st.items():
+                if isinstance(t, torch.Tensor):
+                    st[k] = t.clone()
 
     def _state_run(self, run: List[torch.nn.Parameter]):
+        """The flat (m, v) of ``run``, every parameter's ``exp_avg`` / ``exp_avg_sq`` a view
+        of them and every parameter with a step counter of its own.  ``self.state`` is the
+        truth: a cached pair is reused only while every parameter's moments are still the
+        views of it this method made (a run that was split and rejoined has newer moments
+        in the buffers of its parts); otherwise the pair is rebuilt from ``self.state``."""
         key = tuple(id(p) for p in run)
         cached = self._flat_state.get(key)
         if cached is not None:
-            return cached
+            mp, vp = cached[0].data_ptr(), cached[1].data_ptr()
+            for p in run:
+                st = self.state[p]
+                a, b = st.get("exp_avg"), st.get("exp_avg_sq")
+                if (a is None or b is None or a.data_ptr() != mp or b.data_ptr() != vp or a.shape != p.shape
+                        or b.shape != p.shape or "step" not in st):
+                    break
+                mp += 4 * p.numel()
+                vp += 4 * p.numel()
+            else:
+                return cached
+        # (re)build: every cached pair that holds one of these parameters goes stale now
+        ids = set(key)
+        for k in [k for k in self._flat_state if ids.intersection(k)]:
+            del self._flat_state[k]
         n = sum(p.numel() for p in run)
         dev = run[0].device
         m = torch.zeros(n, device=dev, dtype=torch.float32)
@@ -131,10 +158,20 @@ class FusedAdam(torch.optim.Optimizer):
                 v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
             st["exp_avg"] = m[off:off + k].view(p.shape)
             st["exp_avg_sq"] = v[off:off + k].view(p.shape)
-            st.setdefault("step", torch.zeros((), dtype=torch.float32))
+            # one counter per parameter, as torch's Adam keeps them: an adopted one is cloned
+            # (a tensor shared with another parameter would advance once per holder)
+            s = st.get("step")
+            st["step"] = (s.clone() if isinstance(s, torch.Tensor)
+                          else torch.tensor(float(s or 0), dtype=torch.float32))
             off += k
         self._flat_state[key] = (m, v)
         return m, v
+
+    def _steps_done(self, p: torch.Tensor) -> int:
+        """The Adam steps ``p`` has taken (0 before its first)."""
+        st = self.state.get(p)
+        s = st.get("step") if st else None
+        return 0 if s is None else int(s)
 
     def _nerf_runs(self, params: List[torch.Tensor]):
         """[(run, pflat, gflat, net)] when ``params`` is a concatenation of whole NeRF
@@ -219,9 +256,11 @@ class FusedAdam(torch.optim.Optimizer):
         for group in self.param_groups:
             b1, b2 = group["betas"]
             params = [p for p in group["params"] if p.grad is not None]
-            # runs must agree on memory layout AND on the clip group
+            # runs must agree on memory layout, on the clip group AND on the step count (one
+            # pair of bias corrections per launch; torch's Adam counts per parameter)
             fast = self._nerf_runs(params)
             if fast is not None and any(len({clip_of.get(id(p), (None,))[0] for p in run}) != 1
+                                        or len({self._steps_done(p) for p in run}) != 1
                                         for run, _, _, _ in fast):
                 fast = None
             if fast is not None:
@@ -231,7 +270,8 @@ class FusedAdam(torch.optim.Optimizer):
                 for run in _runs(params):
                     cur = [run[0]]
                     for p in run[1:]:
-                        if clip_of.get(id(p), (None,))[0] == clip_of.get(id(cur[0]), (None,))[0]:
+                        if (clip_of.get(id(p), (None,))[0] == clip_of.get(id(cur[0]), (None,))[0]
+                                and self._steps_done(p) == self._steps_done(cur[0])):
                             cur.append(p)
                         else:
                             runs.append((cur, None, None))
@@ -248,11 +288,10 @@ class FusedAdam(torch.optim.Optimizer):
                     if gflat is None or gflat.data_ptr() % 16:
                         gflat = torch.cat([p.grad.reshape(-1) for p in run])
                 m, v = self._state_run(run)
-                st = self.state[run[0]]
-                st["step"] += 1
-                step = int(st["step"].item()) if st["step"].device.type == "cpu" else int(st["step"])
-                for p in run[1:]:
-                    self.state[p]["step"] = st["step"]
+                steps = [self.state[p]["step"] for p in run]
+                step = int(steps[0]) + 1
+                assert all(int(s) + 1 == step for s in steps[1:]), "FusedAdam: a run at different steps"
+                torch._foreach_add_(steps, 1)
                 span = {"p": pflat, "g": gflat, "m": m, "v": v}
                 clip = clip_of.get(id(run[0]))
                 if clip is not None:
