@@ -3,20 +3,31 @@
 // Reference semantics (ShawnnnLiu/Robust-NeRF):
 //   raw2outputs  noisy_src/rendering.py:20-116
 //   loss         noisy_src/train.py:89,98 (mean((rgb - target)^2))
-// One thread per ray walks its S samples in order, so the transmittance is the
-// same sequential product as torch's CPU cumprod:
 //   delta_i = (z_{i+1} - z_i | 1e10) * |d|;  a_i = 1 - exp(-relu(sigma_i + n_i) * delta_i)
 //   T_0 = 1, T_{i+1} = T_i * (1 - a_i + 1e-10);  w_i = a_i T_i
 //   rgb = sum w c (+ 1 - acc if white), depth = sum w z, acc = sum w.
 // Backward uses the division-free form of torch's cumprod gradient:
 //   dL/da_i = T_i (G_i - R_i),  R_i = G_{i+1} a_{i+1} + t_{i+1} R_{i+1},  R_{S-1} = 0
 // (equal to G_i T_i - (sum_{k>i} G_k w_k) / t_i, the formula autograd evaluates).
+//
+// Every expression is written once, as a __device__ piece, and the kernels only order them:
+//   thread per ray  composite_fwd_kernel, composite_bwd_kernel (S > 64 kCompK): the serial
+//                   walk, the transmittance the same sequential product as torch's CPU cumprod
+//   wave per ray    gather_lane -> wave_excl_product -> forward_sums    composite_fwd_wave_kernel
+//                   gather_lane -> wave_excl_product -> backward_tail   composite_bwd_wave_kernel
+//                   all four, with the loss seed before the tail        composite_mse_wave_kernel
+// Seams: gather_lane's per-sample hook (the backward computes G there, the fused kernel keeps
+// colour and z in registers); forward_sums' colour / z source (memory or those registers);
+// backward_tail's Seed and G, passed as values, so absent upstream gradients are the zeros the
+// separate kernels read.  Another photometric loss replaces only the "loss seed" lines of
+// composite_mse_ray (mse_grad and sqerr).  A wave form for longer rays is a loop around the
+// same pieces that carries E and X from one segment of 64 kCompK samples to the next.
 #include "common.hpp"
 
 namespace nr {
 
 struct SampleTerms {
-    float delta_raw, alpha, e, sig;  // sig = relu'd sigma after noise
+    float delta_raw, alpha, e, sig, t;  // sig = relu'd sigma after noise, t = 1 - alpha + 1e-10
 };
 
 __device__ __forceinline__ SampleTerms sample_terms(const float* sigma, const float* z, const float* noise,
@@ -28,7 +39,87 @@ __device__ __forceinline__ SampleTerms sample_terms(const float* sigma, const fl
     t.sig = s > 0.f ? s : 0.f;
     t.e = expf(-t.sig * (t.delta_raw * dnorm));
     t.alpha = 1.0f - t.e;
+    t.t = 1.0f - t.alpha + 1e-10f;
     return t;
+}
+
+// ---- per-ray pieces, shared by the thread-per-ray and the wave-per-ray kernels
+struct Ray {
+    int b;
+    int64_t base;  // b * S: the global index of the ray's first sample
+    float dx, dy, dz, dnorm;
+};
+
+__device__ __forceinline__ Ray load_ray(const float* rd, int b, int S) {
+    Ray r;
+    r.b = b;
+    r.base = static_cast<int64_t>(b) * S;
+    r.dx = rd[3 * b], r.dy = rd[3 * b + 1], r.dz = rd[3 * b + 2];
+    r.dnorm = norm3(r.dx, r.dy, r.dz);
+    return r;
+}
+
+// The upstream gradients of one ray; the white background folds -(gr + gg + gb) into ga.
+struct Seed { float gr, gg, gb, gd, ga; };
+
+__device__ __forceinline__ Seed upstream_seed(float gr, float gg, float gb, float gd, float g_acc, int white) {
+    return {gr, gg, gb, gd, g_acc - (white ? (gr + gg) + gb : 0.f)};
+}
+
+__device__ __forceinline__ Seed load_seed(const float* g_map, const float* g_depth, const float* g_acc, int b,
+                                          int white) {
+    return upstream_seed(g_map[3 * b], g_map[3 * b + 1], g_map[3 * b + 2], g_depth ? g_depth[b] : 0.f,
+                         g_acc ? g_acc[b] : 0.f, white);
+}
+
+struct ColourZ { float c0, c1, c2, z; };
+
+__device__ __forceinline__ ColourZ load_colour_z(const float* rgb, const float* z, int64_t i) {
+    return {rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], z[i]};
+}
+
+// G_i = dL/dw_i of sample i (global index i for the optional g_w).
+__device__ __forceinline__ float upstream_G(const Seed& sd, const ColourZ& s, const float* g_w, int64_t i) {
+    float G = ((sd.gr * s.c0 + sd.gg * s.c1) + sd.gb * s.c2) + sd.gd * s.z + sd.ga;
+    if (g_w) G += g_w[i];
+    return G;
+}
+
+struct Maps { float r, g, bl, d, a; };
+
+__device__ __forceinline__ void accumulate(Maps& m, float w, const ColourZ& s) {
+    m.r += w * s.c0, m.g += w * s.c1, m.bl += w * s.c2;
+    m.d += w * s.z, m.a += w;
+}
+
+__device__ __forceinline__ void white_fixup(Maps& m, int white) {
+    if (white) m.r = m.r + (1.0f - m.a), m.g = m.g + (1.0f - m.a), m.bl = m.bl + (1.0f - m.a);
+}
+
+__device__ __forceinline__ void store_maps(const Maps& m, int b, float* rgb_map, float* depth, float* acc) {
+    rgb_map[3 * b] = m.r, rgb_map[3 * b + 1] = m.g, rgb_map[3 * b + 2] = m.bl;
+    if (depth) depth[b] = m.d;
+    if (acc) acc[b] = m.a;
+}
+
+// The gradient stores of sample i (global index) from its transmittance Ti and its
+// recurrence value R; the sample's term of g_norm goes to gn64 (see wave_sum_f64).
+__device__ __forceinline__ void store_sample_grads(const Seed& sd, float dnorm, int64_t i, float Ti,
+                                                   const SampleTerms& st, float G, float R, float* g_rgb,
+                                                   float* g_sigma, bool want_norm, double& gn64) {
+    const float w = st.alpha * Ti;
+    g_rgb[3 * i] = sd.gr * w, g_rgb[3 * i + 1] = sd.gg * w, g_rgb[3 * i + 2] = sd.gb * w;
+    const float g_alpha = Ti * (G - R);
+    // alpha = 1 - exp(x), x = -relu(s) * delta_raw * |d|
+    const float g_x = -g_alpha * st.e;
+    g_sigma[i] = (st.sig > 0.f) ? -g_x * (st.delta_raw * dnorm) : 0.f;
+    if (want_norm) gn64 += static_cast<double>(g_x * (-st.sig * st.delta_raw));
+}
+
+__device__ __forceinline__ void add_g_rd(float* g_rd, const Ray& ray, float g_norm) {
+    g_rd[3 * ray.b] += g_norm * ray.dx / ray.dnorm;
+    g_rd[3 * ray.b + 1] += g_norm * ray.dy / ray.dnorm;
+    g_rd[3 * ray.b + 2] += g_norm * ray.dz / ray.dnorm;
 }
 
 __global__ void composite_fwd_kernel(const float* rgb, const float* sigma, const float* z, const float* rd,
@@ -36,31 +127,18 @@ __global__ void composite_fwd_kernel(const float* rgb, const float* sigma, const
                                      float* acc, float* weights) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const float dnorm = sqrtf(rd[3 * b] * rd[3 * b] + rd[3 * b + 1] * rd[3 * b + 1] + rd[3 * b + 2] * rd[3 * b + 2]);
-    const int64_t base = static_cast<int64_t>(b) * S;
-    float T = 1.0f, r = 0.f, g = 0.f, bl = 0.f, d = 0.f, a = 0.f;
+    const Ray ray = load_ray(rd, b, S);
+    float T = 1.0f;
+    Maps m = {};
     for (int i = 0; i < S; ++i) {
-        const SampleTerms st = sample_terms(sigma, z, noise, base, i, S, dnorm);
+        const SampleTerms st = sample_terms(sigma, z, noise, ray.base, i, S, ray.dnorm);
         const float w = st.alpha * T;
-        T = T * (1.0f - st.alpha + 1e-10f);
-        if (weights) weights[base + i] = w;
-        const int64_t q = 3 * (base + i);
-        r += w * rgb[q];
-        g += w * rgb[q + 1];
-        bl += w * rgb[q + 2];
-        d += w * z[base + i];
-        a += w;
+        T = T * st.t;
+        if (weights) weights[ray.base + i] = w;
+        accumulate(m, w, load_colour_z(rgb, z, ray.base + i));
     }
-    if (white) {
-        r = r + (1.0f - a);
-        g = g + (1.0f - a);
-        bl = bl + (1.0f - a);
-    }
-    rgb_map[3 * b] = r;
-    rgb_map[3 * b + 1] = g;
-    rgb_map[3 * b + 2] = bl;
-    if (depth) depth[b] = d;
-    if (acc) acc[b] = a;
+    white_fixup(m, white);
+    store_maps(m, b, rgb_map, depth, acc);
 }
 
 // g_sigma doubles as scratch for T_i between the two passes.
@@ -70,53 +148,32 @@ __global__ void composite_bwd_kernel(const float* rgb, const float* sigma, const
                                      float* g_sigma, float* g_rd) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const float dx = rd[3 * b], dy = rd[3 * b + 1], dz = rd[3 * b + 2];
-    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-    const int64_t base = static_cast<int64_t>(b) * S;
-    const float gr = g_map[3 * b], gg = g_map[3 * b + 1], gb = g_map[3 * b + 2];
-    const float gd = g_depth ? g_depth[b] : 0.f;
-    const float ga = (g_acc ? g_acc[b] : 0.f) - (white ? (gr + gg) + gb : 0.f);
+    const Ray ray = load_ray(rd, b, S);
+    const Seed sd = load_seed(g_map, g_depth, g_acc, b, white);
     // pass 1: transmittance T_i -> g_sigma scratch
     float T = 1.0f;
     for (int i = 0; i < S; ++i) {
-        const SampleTerms st = sample_terms(sigma, z, noise, base, i, S, dnorm);
-        g_sigma[base + i] = T;
-        T = T * (1.0f - st.alpha + 1e-10f);
+        const SampleTerms st = sample_terms(sigma, z, noise, ray.base, i, S, ray.dnorm);
+        g_sigma[ray.base + i] = T;
+        T = T * st.t;
     }
     // pass 2: reverse recurrence
     float R = 0.f, Gn = 0.f, an = 0.f, tn = 0.f;
     double gn64 = 0.0;  // g_norm, summed in fp64 as in the wave kernels (wave_sum_f64)
     for (int i = S - 1; i >= 0; --i) {
-        const SampleTerms st = sample_terms(sigma, z, noise, base, i, S, dnorm);
-        const int64_t q = 3 * (base + i);
-        const float Ti = g_sigma[base + i];
-        const float w = st.alpha * Ti;
-        const float c0 = rgb[q], c1 = rgb[q + 1], c2 = rgb[q + 2];
-        float G = ((gr * c0 + gg * c1) + gb * c2) + gd * z[base + i] + ga;
-        if (g_w) G += g_w[base + i];
-        g_rgb[q] = gr * w;
-        g_rgb[q + 1] = gg * w;
-        g_rgb[q + 2] = gb * w;
+        const SampleTerms st = sample_terms(sigma, z, noise, ray.base, i, S, ray.dnorm);
+        const float Ti = g_sigma[ray.base + i];
+        const float G = upstream_G(sd, load_colour_z(rgb, z, ray.base + i), g_w, ray.base + i);
         if (i < S - 1) R = Gn * an + tn * R;
-        const float g_alpha = Ti * (G - R);
-        // alpha = 1 - exp(x), x = -relu(s) * delta_raw * |d|
-        const float g_x = -g_alpha * st.e;
-        const float delta = st.delta_raw * dnorm;
-        g_sigma[base + i] = (st.sig > 0.f) ? -g_x * delta : 0.f;
-        if (g_rd) gn64 += static_cast<double>(g_x * (-st.sig * st.delta_raw));
+        store_sample_grads(sd, ray.dnorm, ray.base + i, Ti, st, G, R, g_rgb, g_sigma, g_rd != nullptr, gn64);
         Gn = G;
         an = st.alpha;
-        tn = 1.0f - st.alpha + 1e-10f;
+        tn = st.t;
     }
-    if (g_rd) {
-        const float g_norm = static_cast<float>(gn64);
-        g_rd[3 * b] += g_norm * dx / dnorm;
-        g_rd[3 * b + 1] += g_norm * dy / dnorm;
-        g_rd[3 * b + 2] += g_norm * dz / dnorm;
-    }
+    if (g_rd) add_g_rd(g_rd, ray, static_cast<float>(gn64));
 }
 
-// ---- wave-per-ray forms (S <= 64 * kCompK): one 64-lane wave per ray, lane j
+// ---- wave-per-ray pieces (S <= 64 * kCompK): one 64-lane wave per ray, lane j
 // owns samples [jK, jK + K) (K = ceil(S / 64)), all loads contiguous per lane.
 // Transmittance: lane-local running product times the wave's exclusive product
 // scan of the per-lane products (the thread-per-ray kernels above walk the ray
@@ -146,121 +203,68 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void composite_fwd_wave_kernel(const float* rgb, const float* sigma,
-                                                                 const float* z, const float* rd,
-                                                                 const float* noise, int B, int S, int K,
-                                                                 int white, float* rgb_map, float* depth,
-                                                                 float* acc, float* weights) {
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (b >= B) return;  // wave-uniform
-    const float dnorm = sqrtf(rd[3 * b] * rd[3 * b] + rd[3 * b + 1] * rd[3 * b + 1] + rd[3 * b + 2] * rd[3 * b + 2]);
-    const int64_t base = static_cast<int64_t>(b) * S;
-    const int i0 = lane * K;
-    float al[kCompK], L[kCompK];
+// The lane's K samples and the lane-local product L of the t before each of them.
+struct Lane {
+    SampleTerms s[kCompK];
+    float L[kCompK];
+};
+
+// Fills ln for samples [i0, i0 + K) and returns the lane's product of t; hook(k, i) runs
+// once per live sample with its global index i.
+template <class Hook>
+__device__ __forceinline__ float gather_lane(Lane& ln, const float* sigma, const float* z, const float* noise,
+                                             const Ray& ray, int i0, int S, int K, Hook&& hook) {
     float P = 1.0f;
 #pragma unroll
     for (int k = 0; k < kCompK; ++k) {
-        al[k] = 0.f;
-        L[k] = P;
+        ln.s[k] = {0.f, 0.f, 1.0f, 0.f, 1.0f};  // past S: delta_raw = 0, a = 0, e = 1, sig = 0, t = 1
+        ln.L[k] = P;
         const int i = i0 + k;
         if (k < K && i < S) {
-            const SampleTerms st = sample_terms(sigma, z, noise, base, i, S, dnorm);
-            al[k] = st.alpha;
-            P = P * (1.0f - st.alpha + 1e-10f);
+            ln.s[k] = sample_terms(sigma, z, noise, ray.base, i, S, ray.dnorm);
+            hook(k, ray.base + i);
+            P = P * ln.s[k].t;
         }
     }
-    // exclusive product scan of P over lanes
-    float incl = P;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float o = __shfl_up(incl, d);
-        if (lane >= d) incl *= o;
-    }
-    float E = __shfl_up(incl, 1);
-    if (lane == 0) E = 1.0f;
-    float r = 0.f, g = 0.f, bl = 0.f, dd = 0.f, a = 0.f;
-#pragma unroll
-    for (int k = 0; k < kCompK; ++k) {
-        const int i = i0 + k;
-        if (k < K && i < S) {
-            const float w = al[k] * (E * L[k]);
-            if (weights) weights[base + i] = w;
-            const int64_t q = 3 * (base + i);
-            r += w * rgb[q];
-            g += w * rgb[q + 1];
-            bl += w * rgb[q + 2];
-            dd += w * z[base + i];
-            a += w;
-        }
-    }
-    r = wave_sum(r);
-    g = wave_sum(g);
-    bl = wave_sum(bl);
-    dd = wave_sum(dd);
-    a = wave_sum(a);
-    if (lane == 0) {
-        if (white) {
-            r = r + (1.0f - a);
-            g = g + (1.0f - a);
-            bl = bl + (1.0f - a);
-        }
-        rgb_map[3 * b] = r;
-        rgb_map[3 * b + 1] = g;
-        rgb_map[3 * b + 2] = bl;
-        if (depth) depth[b] = dd;
-        if (acc) acc[b] = a;
-    }
+    return P;
 }
 
-__global__ __launch_bounds__(256) void composite_bwd_wave_kernel(
-    const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise, int B, int S, int K,
-    int white, const float* g_map, const float* g_depth, const float* g_acc, const float* g_w, float* g_rgb,
-    float* g_sigma, float* g_rd) {
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const float dx = rd[3 * b], dy = rd[3 * b + 1], dz = rd[3 * b + 2];
-    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-    const int64_t base = static_cast<int64_t>(b) * S;
-    const float gr = g_map[3 * b], gg = g_map[3 * b + 1], gb = g_map[3 * b + 2];
-    const float gd = g_depth ? g_depth[b] : 0.f;
-    const float ga = (g_acc ? g_acc[b] : 0.f) - (white ? (gr + gg) + gb : 0.f);
-    const int i0 = lane * K;
-    float al[kCompK], tt[kCompK], ee[kCompK], sg[kCompK], dr[kCompK], GG[kCompK], L[kCompK];
-    float P = 1.0f;
-#pragma unroll
-    for (int k = 0; k < kCompK; ++k) {
-        al[k] = 0.f;
-        tt[k] = 1.0f;
-        ee[k] = 1.0f;
-        sg[k] = 0.f;
-        dr[k] = 0.f;
-        GG[k] = 0.f;
-        L[k] = P;
-        const int i = i0 + k;
-        if (k < K && i < S) {
-            const SampleTerms st = sample_terms(sigma, z, noise, base, i, S, dnorm);
-            al[k] = st.alpha;
-            tt[k] = 1.0f - st.alpha + 1e-10f;
-            ee[k] = st.e;
-            sg[k] = st.sig;
-            dr[k] = st.delta_raw;
-            const int64_t q = 3 * (base + i);
-            float G = ((gr * rgb[q] + gg * rgb[q + 1]) + gb * rgb[q + 2]) + gd * z[base + i] + ga;
-            if (g_w) G += g_w[base + i];
-            GG[k] = G;
-            P = P * tt[k];
-        }
-    }
+// Exclusive product scan of P over the wave's lanes.
+__device__ __forceinline__ float wave_excl_product(float P, int lane) {
     float incl = P;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const float o = __shfl_up(incl, d);
         if (lane >= d) incl *= o;
     }
-    float E = __shfl_up(incl, 1);
-    if (lane == 0) E = 1.0f;
+    const float E = __shfl_up(incl, 1);
+    return lane == 0 ? 1.0f : E;
+}
+
+// The ray's maps, the same in every lane; src(k, i) gives the colour and z of sample k.
+template <class Src>
+__device__ __forceinline__ Maps forward_sums(const Lane& ln, float E, const Ray& ray, int i0, int S, int K,
+                                             int white, float* weights, Src&& src) {
+    Maps m = {};
+#pragma unroll
+    for (int k = 0; k < kCompK; ++k) {
+        const int i = i0 + k;
+        if (k < K && i < S) {
+            const float w = ln.s[k].alpha * (E * ln.L[k]);
+            if (weights) weights[ray.base + i] = w;
+            accumulate(m, w, src(k, ray.base + i));
+        }
+    }
+    m.r = wave_sum(m.r), m.g = wave_sum(m.g), m.bl = wave_sum(m.bl);
+    m.d = wave_sum(m.d), m.a = wave_sum(m.a);
+    white_fixup(m, white);
+    return m;
+}
+
+// g_rgb, g_sigma and the ray's g_rd from the lane's G (0 past S) and the seed.
+__device__ __forceinline__ void backward_tail(const Lane& ln, const float (&GG)[kCompK], float E, const Ray& ray,
+                                              const Seed& sd, int i0, int S, int K, int lane, float* g_rgb,
+                                              float* g_sigma, float* g_rd) {
     // lane-local affine maps R_i = A_i + B_i X (X = R at the lane's last sample)
     float A[kCompK], Bc[kCompK];
     float an = 0.f, bn = 1.0f;
@@ -271,16 +275,16 @@ __global__ __launch_bounds__(256) void composite_bwd_wave_kernel(
                 an = 0.f;
                 bn = 1.0f;
             } else {
-                an = GG[k + 1] * al[k + 1] + tt[k + 1] * an;
-                bn = tt[k + 1] * bn;
+                an = GG[k + 1] * ln.s[k + 1].alpha + ln.s[k + 1].t * an;
+                bn = ln.s[k + 1].t * bn;
             }
         }
         A[k] = an;
         Bc[k] = bn;
     }
     // this lane's map for its predecessor: X_{j-1} = alpha + beta X_j
-    float qa = GG[0] * al[0] + tt[0] * A[0];
-    float qb = tt[0] * Bc[0];
+    float qa = GG[0] * ln.s[0].alpha + ln.s[0].t * A[0];
+    float qb = ln.s[0].t * Bc[0];
     // suffix composition Q_j = N_j o N_{j+1} o ... o N_63
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -296,173 +300,96 @@ __global__ __launch_bounds__(256) void composite_bwd_wave_kernel(
 #pragma unroll
     for (int k = 0; k < kCompK; ++k) {
         const int i = i0 + k;
-        if (k < K && i < S) {
-            const float Ti = E * L[k];
-            const float w = al[k] * Ti;
-            const int64_t q = 3 * (base + i);
-            g_rgb[q] = gr * w;
-            g_rgb[q + 1] = gg * w;
-            g_rgb[q + 2] = gb * w;
-            const float R = A[k] + Bc[k] * X;
-            const float g_alpha = Ti * (GG[k] - R);
-            const float g_x = -g_alpha * ee[k];
-            g_sigma[base + i] = (sg[k] > 0.f) ? -g_x * (dr[k] * dnorm) : 0.f;
-            if (g_rd) gn64 += static_cast<double>(g_x * (-sg[k] * dr[k]));  // launch-uniform
-        }
+        if (k < K && i < S)  // g_rd is launch-uniform
+            store_sample_grads(sd, ray.dnorm, ray.base + i, E * ln.L[k], ln.s[k], GG[k], A[k] + Bc[k] * X, g_rgb,
+                               g_sigma, g_rd != nullptr, gn64);
     }
     const float g_norm = g_rd ? static_cast<float>(wave_sum_f64(gn64)) : 0.f;
-    if (g_rd && lane == 0) {
-        g_rd[3 * b] += g_norm * dx / dnorm;
-        g_rd[3 * b + 1] += g_norm * dy / dnorm;
-        g_rd[3 * b + 2] += g_norm * dz / dnorm;
-    }
+    if (g_rd && lane == 0) add_g_rd(g_rd, ray, g_norm);
 }
 
-// One ray of composite_mse_wave_kernel (lane = the wave's lane).
+__global__ __launch_bounds__(256) void composite_fwd_wave_kernel(const float* rgb, const float* sigma,
+                                                                 const float* z, const float* rd,
+                                                                 const float* noise, int B, int S, int K,
+                                                                 int white, float* rgb_map, float* depth,
+                                                                 float* acc, float* weights) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= B) return;  // wave-uniform
+    const Ray ray = load_ray(rd, b, S);
+    Lane ln;
+    const float P = gather_lane(ln, sigma, z, noise, ray, lane * K, S, K, [](int, int64_t) {});
+    const float E = wave_excl_product(P, lane);
+    const Maps m = forward_sums(ln, E, ray, lane * K, S, K, white, weights,
+                                [&](int, int64_t i) { return load_colour_z(rgb, z, i); });
+    if (lane == 0) store_maps(m, b, rgb_map, depth, acc);
+}
+
+__global__ __launch_bounds__(256) void composite_bwd_wave_kernel(
+    const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise, int B, int S, int K,
+    int white, const float* g_map, const float* g_depth, const float* g_acc, const float* g_w, float* g_rgb,
+    float* g_sigma, float* g_rd) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= B) return;  // wave-uniform
+    const Ray ray = load_ray(rd, b, S);
+    const Seed sd = load_seed(g_map, g_depth, g_acc, b, white);
+    Lane ln;
+    float GG[kCompK] = {};
+    const float P = gather_lane(ln, sigma, z, noise, ray, lane * K, S, K, [&](int k, int64_t i) {
+        GG[k] = upstream_G(sd, load_colour_z(rgb, z, i), g_w, i);
+    });
+    const float E = wave_excl_product(P, lane);
+    backward_tail(ln, GG, E, ray, sd, lane * K, S, K, lane, g_rgb, g_sigma, g_rd);
+}
+
+__device__ __forceinline__ float mse_grad(float d, float inv, float scale) { return (2.0f * d) * inv * scale; }
+
+// One ray of composite_mse_wave_kernel (lane = the wave's lane).  No early return here:
+// the wave still has to reach the barriers of sum_loss_last_block.
 __device__ __forceinline__ void composite_mse_ray(const float* rgb, const float* sigma, const float* z, const float* rd,
                                                   const float* noise, const float* target, int b, int S, int K,
                                                   int white, float inv, float scale, float* rgb_map, float* depth,
                                                   float* acc, float* weights, float* sqerr, float* g_rgb,
                                                   float* g_sigma, float* g_rd, int lane) {
-    const float dx = rd[3 * b], dy = rd[3 * b + 1], dz = rd[3 * b + 2];
-    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-    const int64_t base = static_cast<int64_t>(b) * S;
+    const Ray ray = load_ray(rd, b, S);
     const int i0 = lane * K;
-    float al[kCompK], tt[kCompK], ee[kCompK], sg[kCompK], dr[kCompK], L[kCompK], c[kCompK][3], zz[kCompK];
-    float P = 1.0f;
-#pragma unroll
-    for (int k = 0; k < kCompK; ++k) {
-        al[k] = 0.f;
-        tt[k] = 1.0f;
-        ee[k] = 1.0f;
-        sg[k] = 0.f;
-        dr[k] = 0.f;
-        zz[k] = 0.f;
-        c[k][0] = c[k][1] = c[k][2] = 0.f;
-        L[k] = P;
-        const int i = i0 + k;
-        if (k < K && i < S) {
-            const SampleTerms st = sample_terms(sigma, z, noise, base, i, S, dnorm);
-            al[k] = st.alpha;
-            tt[k] = 1.0f - st.alpha + 1e-10f;
-            ee[k] = st.e;
-            sg[k] = st.sig;
-            dr[k] = st.delta_raw;
-            zz[k] = z[base + i];
-            const int64_t q = 3 * (base + i);
-            c[k][0] = rgb[q];
-            c[k][1] = rgb[q + 1];
-            c[k][2] = rgb[q + 2];
-            P = P * tt[k];
-        }
-    }
-    float incl = P;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float o = __shfl_up(incl, d);
-        if (lane >= d) incl *= o;
-    }
-    float E = __shfl_up(incl, 1);
-    if (lane == 0) E = 1.0f;
-    // forward
-    float r = 0.f, g = 0.f, bl = 0.f, dd = 0.f, a = 0.f;
-#pragma unroll
-    for (int k = 0; k < kCompK; ++k) {
-        const int i = i0 + k;
-        if (k < K && i < S) {
-            const float w = al[k] * (E * L[k]);
-            if (weights) weights[base + i] = w;
-            r += w * c[k][0];
-            g += w * c[k][1];
-            bl += w * c[k][2];
-            dd += w * zz[k];
-            a += w;
-        }
-    }
-    r = wave_sum(r);
-    g = wave_sum(g);
-    bl = wave_sum(bl);
-    dd = wave_sum(dd);
-    a = wave_sum(a);
-    if (white) {
-        r = r + (1.0f - a);
-        g = g + (1.0f - a);
-        bl = bl + (1.0f - a);
-    }
+    Lane ln;
+    ColourZ cz[kCompK] = {};
+    const float P = gather_lane(ln, sigma, z, noise, ray, i0, S, K,
+                                [&](int k, int64_t i) { cz[k] = load_colour_z(rgb, z, i); });
+    const float E = wave_excl_product(P, lane);
+    const Maps m = forward_sums(ln, E, ray, i0, S, K, white, weights, [&](int k, int64_t) { return cz[k]; });
     // loss seed
-    const float d0 = r - target[3 * b], d1 = g - target[3 * b + 1], d2 = bl - target[3 * b + 2];
-    const float gr = (2.0f * d0) * inv * scale, gg = (2.0f * d1) * inv * scale, gb = (2.0f * d2) * inv * scale;
+    const float d0 = m.r - target[3 * b], d1 = m.g - target[3 * b + 1], d2 = m.bl - target[3 * b + 2];
+    const Seed sd = upstream_seed(mse_grad(d0, inv, scale), mse_grad(d1, inv, scale), mse_grad(d2, inv, scale), 0.f,
+                                  0.f, white);
     if (lane == 0) {
-        rgb_map[3 * b] = r;
-        rgb_map[3 * b + 1] = g;
-        rgb_map[3 * b + 2] = bl;
-        if (depth) depth[b] = dd;
-        if (acc) acc[b] = a;
+        store_maps(m, b, rgb_map, depth, acc);
         sqerr[b] = (d0 * d0 + d1 * d1) + d2 * d2;
     }
     // backward (composite_bwd_wave_kernel with g_depth = g_acc = g_w = 0)
-    const float gd = 0.f;
-    const float ga = 0.f - (white ? (gr + gg) + gb : 0.f);
     float GG[kCompK];
 #pragma unroll
     for (int k = 0; k < kCompK; ++k) {
         GG[k] = 0.f;
-        if (k < K && i0 + k < S) GG[k] = ((gr * c[k][0] + gg * c[k][1]) + gb * c[k][2]) + gd * zz[k] + ga;
+        if (k < K && i0 + k < S) GG[k] = upstream_G(sd, cz[k], nullptr, 0);
     }
-    float A[kCompK], Bc[kCompK];
-    float an = 0.f, bn = 1.0f;
-#pragma unroll
-    for (int k = kCompK - 1; k >= 0; --k) {
-        if (k < K) {
-            if (k == K - 1) {
-                an = 0.f;
-                bn = 1.0f;
-            } else {
-                an = GG[k + 1] * al[k + 1] + tt[k + 1] * an;
-                bn = tt[k + 1] * bn;
-            }
-        }
-        A[k] = an;
-        Bc[k] = bn;
-    }
-    float qa = GG[0] * al[0] + tt[0] * A[0];
-    float qb = tt[0] * Bc[0];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float oa = __shfl_down(qa, d), ob = __shfl_down(qb, d);
-        if (lane + d < 64) {
-            qa = qa + qb * oa;
-            qb = qb * ob;
-        }
-    }
-    float X = __shfl_down(qa, 1);
-    if (lane == 63) X = 0.f;
-    double gn64 = 0.0;  // g_norm: see wave_sum_f64
-#pragma unroll
-    for (int k = 0; k < kCompK; ++k) {
-        const int i = i0 + k;
-        if (k < K && i < S) {
-            const float Ti = E * L[k];
-            const float w = al[k] * Ti;
-            const int64_t q = 3 * (base + i);
-            g_rgb[q] = gr * w;
-            g_rgb[q + 1] = gg * w;
-            g_rgb[q + 2] = gb * w;
-            const float R = A[k] + Bc[k] * X;
-            const float g_alpha = Ti * (GG[k] - R);
-            const float g_x = -g_alpha * ee[k];
-            g_sigma[base + i] = (sg[k] > 0.f) ? -g_x * (dr[k] * dnorm) : 0.f;
-            if (g_rd) gn64 += static_cast<double>(g_x * (-sg[k] * dr[k]));  // launch-uniform
-        }
-    }
-    const float g_norm = g_rd ? static_cast<float>(wave_sum_f64(gn64)) : 0.f;
-    if (g_rd && lane == 0) {
-        g_rd[3 * b] += g_norm * dx / dnorm;
-        g_rd[3 * b + 1] += g_norm * dy / dnorm;
-        g_rd[3 * b + 2] += g_norm * dz / dnorm;
-    }
+    backward_tail(ln, GG, E, ray, sd, i0, S, K, lane, g_rgb, g_sigma, g_rd);
 }
 
+// Sum of v over the workgroup in a fixed order: xor butterfly within each wave, lane 0 of
+// each wave to part[wave], one barrier, the waves added in index order from 0.f.  The
+// result is thread 0's alone; part holds at least blockDim.x / 64 floats.
+__device__ __forceinline__ float block_sum_ordered(float v, float* part) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float tot = 0.f;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) tot += part[w];
+    return tot;
+}
 
 // The last workgroup to finish (an agent-scope ticket; the recipe of
 // cdna_hip_programming.md §6 Guideline 16: plain stores, release fence, relaxed
@@ -488,12 +415,8 @@ __device__ __forceinline__ void sum_loss_last_block(const float* sqerr, int B, f
     __syncthreads();
     float sum = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) sum += sqerr[i];
-    sum = wave_sum(sum);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sum;
-    __syncthreads();
+    const float tot = block_sum_ordered(sum, part);
     if (threadIdx.x == 0) {
-        float tot = 0.f;
-        for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) tot += part[w];
         *loss = tot * inv;
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -501,13 +424,16 @@ __device__ __forceinline__ void sum_loss_last_block(const float* sqerr, int B, f
 
 // Training form: raw2outputs (rendering.py:20-116) + the MSE loss seed (train.py:89,98:
 // mean over 3B of (rgb_map - target)^2, gradient 2 (rgb_map - target) / 3B * scale) + the
-// backward of both, in one wave-per-ray pass.  Every value is the expression
-// composite_fwd_wave_kernel, mse_kernel and composite_bwd_wave_kernel evaluate (the
-// backward's depth / acc / weight terms are the zeros those kernels read for absent
-// gradients), so g_rgb / g_sigma / g_rd are bit-identical to the three launches.  The
-// loss is summed per ray (sqerr), then over the rays by the last workgroup (ticket) or,
-// without a ticket, by loss_sum_kernel.
-__global__ __launch_bounds__(256) void composite_mse_wave_kernel(
+// backward of both, in one wave-per-ray pass.  It runs the pieces the forward and the
+// backward wave kernels run, with mse_kernel's mse_grad in between (the backward's depth /
+// acc / weight terms are the zeros those kernels read for absent gradients), so g_rgb /
+// g_sigma / g_rd are bit-identical to the three launches.  The loss is summed per ray
+// (sqerr), then over the rays by the last workgroup (ticket) or, without a ticket, by
+// loss_sum_kernel.  Dead waves of the last workgroup skip the ray but not the loss sum.
+// Two waves per SIMD, as the kernel ran when its 254 registers allowed no more: a step's
+// 1,024 workgroups are 16 waves per CU, two even rounds; at the three that its 138 registers
+// would allow, the second round runs one wave (measured at S = 192: 17.9 against 17.0 us).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void composite_mse_wave_kernel(
     const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise, const float* target,
     int B, int S, int K, int white, float inv, float scale, float* rgb_map, float* depth, float* acc, float* weights,
     float* sqerr, float* g_rgb, float* g_sigma, float* g_rd, unsigned* ticket, float* loss) {
@@ -523,14 +449,8 @@ __global__ __launch_bounds__(1024) void loss_sum_kernel(const float* sqerr, int 
     __shared__ float part[16];
     float s = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) s += sqerr[i];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tot = 0.f;
-        for (int i = 0; i < static_cast<int>(blockDim.x >> 6); ++i) tot += part[i];
-        *loss = tot * inv;
-    }
+    const float tot = block_sum_ordered(s, part);
+    if (threadIdx.x == 0) *loss = tot * inv;
 }
 
 // loss = mean((p - t)^2) over n = 3B; g = 2 (p - t) / n * scale.  One block.
@@ -541,17 +461,23 @@ __global__ void mse_kernel(const float* p, const float* t, int n, float scale, f
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const float d = p[i] - t[i];
         s += d * d;
-        if (g) g[i] = (2.0f * d) * inv * scale;
+        if (g) g[i] = mse_grad(d, inv, scale);
     }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) part[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0 && loss) {
-        float tot = 0.f;
-        for (int i = 0; i < static_cast<int>(blockDim.x >> 6); ++i) tot += part[i];
-        *loss = tot * inv;
-    }
+    const float tot = block_sum_ordered(s, part);
+    if (threadIdx.x == 0 && loss) *loss = tot * inv;
+}
+
+// Wave per ray up to 64 * kCompK samples (K per lane, four rays per workgroup), thread
+// per ray beyond.
+struct CompositeForm {
+    bool wave;
+    int K;
+    dim3 grid, block;
+};
+
+static CompositeForm composite_form(int B, int S) {
+    const bool wave = S <= 64 * kCompK;
+    return {wave, (S + 63) / 64, dim3(ceil_div(B, wave ? 4 : 64)), dim3(wave ? 256 : 64)};
 }
 
 }  // namespace nr
@@ -565,13 +491,14 @@ int nr_composite_fwd(const float* rgb, const float* sigma, const float* z, const
                      nr_stream_t stream) {
     NR_REQUIRE(rgb && sigma && z && rd && rgb_map && B >= 0 && S > 0, "nr_composite_fwd: bad arguments");
     if (B == 0) return NR_OK;
-    if (S <= 64 * kCompK)
-        hipLaunchKernelGGL(composite_fwd_wave_kernel, dim3(ceil_div(B, 4)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), rgb, sigma, z, rd, noise, B, S, (S + 63) / 64, white,
+    const CompositeForm f = composite_form(B, S);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (f.wave)
+        hipLaunchKernelGGL(composite_fwd_wave_kernel, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, B, S, f.K, white,
                            rgb_map, depth, acc, weights);
     else
-        hipLaunchKernelGGL(composite_fwd_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, static_cast<hipStream_t>(stream),
-                           rgb, sigma, z, rd, noise, B, S, white, rgb_map, depth, acc, weights);
+        hipLaunchKernelGGL(composite_fwd_kernel, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, B, S, white, rgb_map,
+                           depth, acc, weights);
     NR_LAUNCH_CHECK("nr_composite_fwd");
     return NR_OK;
 }
@@ -582,13 +509,14 @@ int nr_composite_bwd(const float* rgb, const float* sigma, const float* z, const
     NR_REQUIRE(rgb && sigma && z && rd && g_map && g_rgb && g_sigma && B >= 0 && S > 0,
                "nr_composite_bwd: bad arguments");
     if (B == 0) return NR_OK;
-    if (S <= 64 * kCompK)
-        hipLaunchKernelGGL(composite_bwd_wave_kernel, dim3(ceil_div(B, 4)), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), rgb, sigma, z, rd, noise, B, S, (S + 63) / 64, white,
+    const CompositeForm f = composite_form(B, S);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (f.wave)
+        hipLaunchKernelGGL(composite_bwd_wave_kernel, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, B, S, f.K, white,
                            g_map, g_depth, g_acc, g_w, g_rgb, g_sigma, g_rd);
     else
-        hipLaunchKernelGGL(composite_bwd_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, static_cast<hipStream_t>(stream),
-                           rgb, sigma, z, rd, noise, B, S, white, g_map, g_depth, g_acc, g_w, g_rgb, g_sigma, g_rd);
+        hipLaunchKernelGGL(composite_bwd_kernel, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, B, S, white, g_map,
+                           g_depth, g_acc, g_w, g_rgb, g_sigma, g_rd);
     NR_LAUNCH_CHECK("nr_composite_bwd");
     return NR_OK;
 }
@@ -602,14 +530,15 @@ int nr_composite_mse(const float* rgb, const float* sigma, const float* z, const
     const hipStream_t s = static_cast<hipStream_t>(stream);
     float* sqerr = static_cast<float*>(workspace);
     const float inv = 1.0f / static_cast<float>(3 * B);
+    const CompositeForm f = composite_form(B, S);
     // the in-launch loss sum pays up to ~256 workgroups; beyond, the agent-scope release and
     // ticket of every workgroup cost more than a second one-block launch (measured: 1024
     // workgroups, 4096 rays, 61 vs 26 + 5 us)
     if (ticket && ceil_div(B, 4) > 256) ticket = nullptr;
-    if (S <= 64 * kCompK) {
-        hipLaunchKernelGGL(composite_mse_wave_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, s, rgb, sigma, z, rd, noise,
-                           target, B, S, (S + 63) / 64, white, inv, scale, rgb_map, depth, acc, weights, sqerr, g_rgb,
-                           g_sigma, g_rd, ticket, loss);
+    if (f.wave) {
+        hipLaunchKernelGGL(composite_mse_wave_kernel, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, target, B, S,
+                           f.K, white, inv, scale, rgb_map, depth, acc, weights, sqerr, g_rgb, g_sigma, g_rd, ticket,
+                           loss);
         NR_LAUNCH_CHECK("nr_composite_mse");
         if (!ticket) {
             hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, s, sqerr, B, inv, loss);

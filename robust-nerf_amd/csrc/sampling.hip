@@ -140,6 +140,42 @@ __device__ __forceinline__ void bitonic_sort(float (&v)[R], int lane) {
     if constexpr (K < R * 64) bitonic_sort<R, K * 2>(v, lane);
 }
 
+// The ray's origin and direction (loaded only when an output needs them) and its unit view
+// direction (rendering.py:165, expand_viewdirs_kernel's values).
+struct RayFrame {
+    float ox, oy, oz, dx, dy, dz, vx, vy, vz;
+};
+
+__device__ __forceinline__ RayFrame ray_frame(const float* ro, const float* rd, int64_t b, const float* pts_out,
+                                              const float* vd_out) {
+    RayFrame f = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (pts_out || vd_out) {
+        f.ox = ro ? ro[3 * b] : 0.f, f.oy = ro ? ro[3 * b + 1] : 0.f, f.oz = ro ? ro[3 * b + 2] : 0.f;
+        f.dx = rd[3 * b], f.dy = rd[3 * b + 1], f.dz = rd[3 * b + 2];
+    }
+    if (vd_out) {
+        const float dn = norm3(f.dx, f.dy, f.dz);
+        f.vx = f.dx / dn, f.vy = f.dy / dn, f.vz = f.dz / dn;
+    }
+    return f;
+}
+
+// Sample o of the output (o = ray * T + place): its depth, point and view direction.
+__device__ __forceinline__ void store_sample(const RayFrame& f, int64_t o, float zv, float* zf_out, float* pts_out,
+                                             float* vd_out) {
+    zf_out[o] = zv;
+    if (pts_out) {
+        pts_out[3 * o] = f.ox + f.dx * zv;
+        pts_out[3 * o + 1] = f.oy + f.dy * zv;
+        pts_out[3 * o + 2] = f.oz + f.dz * zv;
+    }
+    if (vd_out) {
+        vd_out[3 * o] = f.vx;
+        vd_out[3 * o + 1] = f.vy;
+        vd_out[3 * o + 2] = f.vz;
+    }
+}
+
 // One wave per ray.  The wave's T = Nc + Nf values (coarse z, then the inverse-CDF
 // samples) live in registers, R = P / 64 per lane for the padded length P (+inf past T),
 // and are sorted there: the LDS form (v1) spent 11-14 us of 19-26 in its 36 LDS
@@ -193,33 +229,11 @@ __global__ void sample_hier_kernel(const float* ro, const float* rd, const float
     }
     bitonic_sort<R>(v, lane);
     const int64_t ob = static_cast<int64_t>(b) * T;
-    float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
-    if (pts_out || vd_out) {
-        ox = ro ? ro[3 * b] : 0.f, oy = ro ? ro[3 * b + 1] : 0.f, oz = ro ? ro[3 * b + 2] : 0.f;
-        dx = rd[3 * b], dy = rd[3 * b + 1], dz = rd[3 * b + 2];
-    }
-    float vx = 0.f, vy = 0.f, vz = 0.f;
-    if (vd_out) {  // rendering.py:165 (expand_viewdirs_kernel's values)
-        const float dn = norm3(dx, dy, dz);
-        vx = dx / dn, vy = dy / dn, vz = dz / dn;
-    }
+    const RayFrame fr = ray_frame(ro, rd, b, pts_out, vd_out);
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         const int e = i * 64 + lane;
-        if (e < T) {
-            const int64_t o = ob + e;
-            zf_out[o] = v[i];
-            if (pts_out) {
-                pts_out[3 * o] = ox + dx * v[i];
-                pts_out[3 * o + 1] = oy + dy * v[i];
-                pts_out[3 * o + 2] = oz + dz * v[i];
-            }
-            if (vd_out) {
-                vd_out[3 * o] = vx;
-                vd_out[3 * o + 1] = vy;
-                vd_out[3 * o + 2] = vz;
-            }
-        }
+        if (e < T) store_sample(fr, ob + e, v[i], zf_out, pts_out, vd_out);
     }
 }
 
@@ -344,16 +358,7 @@ __global__ __launch_bounds__(kLongThreads) void sample_hier_long_kernel(const fl
     }
     __syncthreads();
     const int64_t ob = b * T;
-    float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
-    if (pts_out || vd_out) {
-        ox = ro ? ro[3 * b] : 0.f, oy = ro ? ro[3 * b + 1] : 0.f, oz = ro ? ro[3 * b + 2] : 0.f;
-        dx = rd[3 * b], dy = rd[3 * b + 1], dz = rd[3 * b + 2];
-    }
-    float vx = 0.f, vy = 0.f, vz = 0.f;
-    if (vd_out) {  // rendering.py:165 (expand_viewdirs_kernel's values)
-        const float dn = norm3(dx, dy, dz);
-        vx = dx / dn, vy = dy / dn, vz = dz / dn;
-    }
+    const RayFrame fr = ray_frame(ro, rd, b, pts_out, vd_out);
     // Sorted position p = r * kRun + i is a real element exactly when p < T.  Four
     // elements per thread keep four independent search chains in flight; every search is
     // the same ten probes of a kRun-long run, so the wave never diverges.
@@ -396,20 +401,8 @@ __global__ __launch_bounds__(kLongThreads) void sample_hier_long_kernel(const fl
 #pragma unroll
         for (int k = 0; k < E; ++k) {
             const int p = base + k * kLongThreads + tid;
-            if (p < T) {  // rank < T: own index plus at most every real element of the other runs
-                const int64_t o = ob + rank[k];
-                zf_out[o] = x[k];
-                if (pts_out) {
-                    pts_out[3 * o] = ox + dx * x[k];
-                    pts_out[3 * o + 1] = oy + dy * x[k];
-                    pts_out[3 * o + 2] = oz + dz * x[k];
-                }
-                if (vd_out) {
-                    vd_out[3 * o] = vx;
-                    vd_out[3 * o + 1] = vy;
-                    vd_out[3 * o + 2] = vz;
-                }
-            }
+            // rank < T: own index plus at most every real element of the other runs
+            if (p < T) store_sample(fr, ob + rank[k], x[k], zf_out, pts_out, vd_out);
         }
     }
 }
