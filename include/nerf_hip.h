@@ -465,7 +465,29 @@ int nr_composite_mse(const float* rgb, const float* sigma, const float* z,
                      float* g_sigma, float* g_rays_d, uint32_t* ticket,
                      void* workspace, nr_stream_t stream);
 
-/* ---- evaluation image tail  (noisy_src/metrics.py:43-116, inference.py:108-125)
+/* ---- distortion regulariser on the ray weights  (no reference counterpart;
+ *      mip-NeRF 360 eq. 15; additive to ABI 5) -------------------------------
+ * weights, z (B,S): a ray's compositing weights and its sample depths, which
+ * must be nondecreasing and lie in [near, far] (preconditions, not checked).
+ *   s_i = (z_i - near)/(far - near), e_i = s_i (i < S), e_S = 1 (the last
+ *   interval is closed at far), m_i = (e_i + e_{i+1})/2, d_i = e_{i+1} - e_i
+ *   L = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+ * loss (device scalar, OVERWRITTEN): the mean of L over the B rays, without
+ * grad_scale.  loss_rays (B), nullable: L per ray.  g_weights (B,S), nullable,
+ * OVERWRITTEN: grad_scale * d(mean L)/d weights (a buffer of its own, not one
+ * of the inputs); z gets no gradient.  One wave
+ * per ray for every S (two passes over the ray, prefix sums in fp64), then a
+ * one-workgroup launch for the mean in a fixed order: no atomics, bit-identical
+ * from run to run.  workspace: nr_distortion_workspace_bytes(B), no
+ * initialisation needed.  NR_EARG for B < 1, S < 1, S > 4096, far <= near or a
+ * null weights, z, loss or workspace.                                        */
+int64_t nr_distortion_workspace_bytes(int B);
+int nr_distortion_loss(const float* weights, const float* z, int B, int S,
+                       float near, float far, float grad_scale, float* loss,
+                       float* loss_rays, float* g_weights, void* workspace,
+                       nr_stream_t stream);
+
+/* ---- evaluation image tail (noisy_src/metrics.py:43-116, inference.py:108-125)
  * Additive to ABI 5.
  *
  * nr_image_metrics: compute_ssim (metrics.py:48-116) and compute_mse (metrics.py:43-45)

@@ -131,6 +131,8 @@ _SIGNATURES = {
     "nr_composite_mse": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_f, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "nr_mse_fwd_bwd": (c_i, [c_vp, c_vp, c_i, c_f, c_vp, c_vp, c_vp]),
+    "nr_distortion_workspace_bytes": (c_i64, [c_i]),
+    "nr_distortion_loss": (c_i, [c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "nr_image_metrics_workspace_bytes": (c_i64, [c_i, c_i, c_i]),
     "nr_image_metrics": (c_i, [c_vp, c_vp, c_i, c_i, c_i, ctypes.POINTER(c_f), c_d, c_d, c_vp, c_vp, c_vp]),
     "nr_frame_u8": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i64, c_i, c_vp]),

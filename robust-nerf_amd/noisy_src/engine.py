@@ -218,6 +218,24 @@ def _loss_and_metrics(out):
     return loss, metrics
 
 
+def _check_distortion_weight(w) -> float:
+    w = float(w)
+    if not w >= 0.0:
+        raise ValueError(f"distortion_weight must be >= 0, not {w}")
+    return w
+
+
+def _distortion_term(aux, render_config, weight: float, prescale: float):
+    """The distortion loss (ops.distortion_loss) on the RENDERING network's weights, from
+    ``render_rays(..., return_aux=True)``'s second result: the fine pair, or the coarse one
+    when no fine network renders.  The coarse network of a coarse+fine pair is left alone:
+    it is a proposal and has to spread.  The gradient carries ``weight * prescale`` already,
+    so the term joins the backward sum unweighted; the logged loss adds ``weight`` times it."""
+    which = "fine" if "weights_fine" in aux else "coarse"
+    return ops.distortion_loss(aux["weights_" + which], aux["z_" + which], render_config.near, render_config.far,
+                               grad_scale=weight * prescale)
+
+
 class Trainer:
     """One reference training iteration (train.py:68-119) on the HIP kernels.
     ``coarse_stream``: run the coarse network's forward, compositing, loss and backward on
@@ -230,12 +248,16 @@ class Trainer:
     ``AUTO_COARSE_STREAM_RAYS`` rays per step (BASELINE cfg #4's 512 rays per rank: 0.856
     -> 0.802 ms per replay; 1024 rays 1.36 -> 1.34 ms; 2048 and 4096 rays no gain or a
     loss; eager steps lose to the second stream's host cost, profiles/r05_coarse_early_ab.txt).
-    ``coarse_stream="auto"`` applies exactly that rule per step; True / False force it."""
+    ``coarse_stream="auto"`` applies exactly that rule per step; True / False force it.
+    ``distortion_weight`` > 0 adds that multiple of the distortion loss of the rendering
+    network's weights (``_distortion_term``) to the loss; ``metrics["loss_distortion"]`` is
+    its unweighted mean.  At 0 the step launches nothing for it."""
 
     AUTO_COARSE_STREAM_RAYS = 1024
 
     def __init__(self, model_coarse, model_fine, render_config, lr: float = 5e-4, lr_decay: int = 250,
-                 max_norm: float = 1.0, process_group=None, coarse_stream=False):
+                 max_norm: float = 1.0, process_group=None, coarse_stream=False, distortion_weight: float = 0.0):
+        self.distortion_weight = _check_distortion_weight(distortion_weight)
         if coarse_stream not in (True, False, "auto"):
             raise ValueError(f"coarse_stream must be True, False or 'auto', not {coarse_stream!r}")
         self.coarse_stream = coarse_stream if coarse_stream == "auto" else bool(coarse_stream)
@@ -278,15 +300,24 @@ class Trainer:
             early["loss_c"].backward(ops.unit_grad(rays_o.device))
 
         # the MSE losses (train.py:89/98) come out of the compositing (ops.composite_mse)
+        dw = self.distortion_weight
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
-                          t_rand=t_rand, u=u, coarse_stream=cs,
+                          t_rand=t_rand, u=u, return_aux=dw > 0, coarse_stream=cs,
                           coarse_backward=coarse_backward if cs is not None else None,
                           target_rgb=target_rgb, loss_scale=gs)
+        dist = None
+        if dw > 0:
+            out, aux = out
+            dist = _distortion_term(aux, self.render_config, dw, gs)
         if cs is not None:
             main = torch.cuda.current_stream(rays_o.device)
             loss_f = out["loss_fine"]
             loss_c = early["loss_c"].detach()
             lf = loss_f.detach()
+            term = None
+            if dist is not None:  # the fine chain's: on the main stream, before its backward
+                loss_f = loss_f + dist
+                term = dw * dist.detach()
             fine_done = main.record_event()
             loss_f.backward(ops.unit_grad(rays_o.device))
             # the summed value on the coarse stream, beside the fine backward (the backward
@@ -297,12 +328,21 @@ class Trainer:
             lf.record_stream(cs)
             with torch.cuda.stream(cs):
                 loss = loss_c + lf
+                if term is not None:  # the one-stream step's association: (loss_c + loss_f) + the term
+                    term.record_stream(cs)
+                    loss = loss + term
             loss.record_stream(main)
             main.wait_stream(cs)  # join the coarse chain
             metrics = {"loss_coarse": loss_c, "loss_fine": lf}
         else:
             loss, metrics = _loss_and_metrics(out)
-            loss.backward(ops.unit_grad(loss.device))
+            if dist is None:
+                loss.backward(ops.unit_grad(loss.device))
+            else:
+                (loss + dist).backward(ops.unit_grad(loss.device))
+                loss = loss.detach() + dw * dist.detach()
+        if dist is not None:
+            metrics["loss_distortion"] = dist.detach()
         if self.reducer is not None:
             _finish_and_adopt(self.reducer, (self.model_coarse, self.model_fine),
                               [flat for _, flat in self.reducer.pending])
@@ -345,12 +385,16 @@ class PoseTrainer:
     by the ray kernels from device memory, and its ``log_scale`` joins the pose Adam as a
     clip group of its own (0.1), with the pose learning rate, LambdaLR and delay; its
     gradient is appended to the pose-gradient all-reduce.  At ``log_scale = 0`` the rays,
-    and with them the networks' and poses' updates, are those without it, bit for bit."""
+    and with them the networks' and poses' updates, are those without it, bit for bit.
+
+    ``distortion_weight``: as in ``Trainer``; the term's gradient reaches the poses through the
+    rendering network like the photometric one."""
 
     def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,
                  lr: float = 5e-4, pose_lr: float = 1e-4, lr_decay: int = 250,
                  rotation_reg_weight: float = 0.01, translation_reg_weight: float = 0.001, process_group=None,
-                 pe_schedule=None, intrinsics=None):
+                 pe_schedule=None, intrinsics=None, distortion_weight: float = 0.0):
+        self.distortion_weight = _check_distortion_weight(distortion_weight)
         self.pe_schedule = pe_schedule
         self.model_coarse, self.model_fine = model_coarse, model_fine
         self.camera_params, self.pixel_sampler, self.render_config = camera_params, pixel_sampler, render_config
@@ -402,10 +446,18 @@ class PoseTrainer:
         target = pixel_batch.target_rgb
         gs = self.reducer.prescale if self.reducer is not None else 1.0  # DP: 1/world in the seed
         # the MSE losses (train_pose_opt.py:355-370) come out of the compositing
+        dw = self.distortion_weight
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
-                          t_rand=t_rand, u=u, target_rgb=target, loss_scale=gs)
+                          t_rand=t_rand, u=u, return_aux=dw > 0, target_rgb=target, loss_scale=gs)
+        if dw > 0:
+            out, aux = out
         loss, metrics = _loss_and_metrics(out)
         bwd = loss
+        if dw > 0:
+            dist = _distortion_term(aux, self.render_config, dw, gs)
+            metrics["loss_distortion"] = dist.detach()
+            loss = loss + dw * dist.detach()
+            bwd = bwd + dist
         if optimize_poses:
             # the regulariser is replicated on every rank: its gradient carries the seed's
             # 1/world too, so the SUM over the ranks counts it once

@@ -644,3 +644,48 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) 
     """The loss value is always the plain mean; only its gradient carries ``grad_scale``."""
     _check(pred, target)
     return _MSE.apply(pred, target, float(grad_scale))
+
+
+class _Distortion(torch.autograd.Function):
+    """The distortion regulariser of one batch (nr_distortion_loss): the forward's one call
+    also produces ``grad_scale`` times the gradient w.r.t. the weights, which the backward
+    hands over.  The depths get no gradient."""
+
+    @staticmethod
+    def forward(ctx, weights, z, near, far, grad_scale):
+        w, zc = _c(weights), _c(z)
+        B, S = zc.shape
+        dev = zc.device
+        loss = torch.empty((), device=dev, dtype=_f32)
+        g_w = torch.empty(B, S, device=dev, dtype=_f32) if ctx.needs_input_grad[0] else None
+        ws = torch.empty(max(8, int(_hip.load().nr_distortion_workspace_bytes(B))), device=dev, dtype=torch.uint8)
+        call("nr_distortion_loss", ptr(w), ptr(zc), B, S, float(near), float(far), float(grad_scale), ptr(loss), None,
+             ptr(g_w), ptr(ws), _stream())
+        ctx.save_for_backward(g_w)
+        ctx.w_shape = weights.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        (g,) = ctx.saved_tensors
+        if g is None:
+            return None, None, None, None, None
+        # seeded by unit_grad(): gl is exactly 1.0 (no multiply launch), as in _MSE
+        if gl.data_ptr() != _unit.get(gl.device, _NO_UNIT).data_ptr():
+            g = g * gl
+        return g.view(ctx.w_shape), None, None, None, None
+
+
+def distortion_loss(weights: torch.Tensor, z_vals: torch.Tensor, near: float, far: float,
+                    grad_scale: float = 1.0) -> torch.Tensor:
+    """The mip-NeRF 360 distortion loss of the compositing weights (B,S) over their depths
+    z_vals (B,S; nondecreasing, within [near, far]), mean over the rays: per ray
+    sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i over the intervals [s_i, s_{i+1}] of the
+    normalised depths s = (z - near) / (far - near), the last closed at 1 (midpoints m,
+    lengths d).  The value is the plain mean; its gradient, w.r.t. the weights only, carries
+    ``grad_scale``."""
+    _check(weights, z_vals)
+    if weights.shape != z_vals.shape or z_vals.dim() != 2:
+        raise ValueError(f"distortion_loss: weights {tuple(weights.shape)} and z_vals {tuple(z_vals.shape)} must be "
+                         "the same (B, S)")
+    return _Distortion.apply(weights, z_vals.detach(), near, far, float(grad_scale))

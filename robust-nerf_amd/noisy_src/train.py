@@ -192,12 +192,15 @@ def load_checkpoint(checkpoint_path, model_coarse, model_fine, optimizer: Option
 
 def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
           train_data: Optional[BlenderData] = None, val_data: Optional[BlenderData] = None,
-          process_group=None, log=print, graph: bool = False) -> Dict[str, object]:
+          process_group=None, log=print, graph: bool = False,
+          distortion_weight: float = 0.0) -> Dict[str, object]:
     """Reference train.py:307-577.  ``train_data`` / ``val_data`` (optional) replace the
     on-disk scene; ``process_group`` (or a torchrun environment, see ``main``) makes it
     data parallel.  ``graph`` replays the training step from a hipGraph after the first
     iteration (``engine.GraphedTrainer``; same results as eager); with data parallelism
     the RCCL all-reduces are captured into it too (``nccl`` backend only).
+    ``distortion_weight`` > 0 adds that multiple of the distortion loss on the rendering
+    network's ray weights (``engine.Trainer``); it is logged on the console line only.
     Returns the networks, the output directory and the final metrics."""
     import torch.distributed as dist
 
@@ -237,7 +240,7 @@ def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
     # coarse_stream="auto": the coarse chain becomes a second graph branch only in a
     # --graph replay of <= 1024 rays (engine.Trainer), where it pays
     trainer = Trainer(model_coarse, model_fine, config.render, lr=config.train.lr, lr_decay=config.train.lr_decay,
-                      process_group=process_group, coarse_stream="auto")
+                      process_group=process_group, coarse_stream="auto", distortion_weight=distortion_weight)
     optimizer = trainer.optimizer
     lpips_metric = LPIPSMetric(device=device) if rank == 0 else None
     if lpips_metric is not None and not lpips_metric.available:
@@ -252,7 +255,7 @@ def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
                              "seed": nc.seed if nc else None, "has_noise": nc.has_noise if nc else False},
             "num_iterations": config.train.num_iterations, "batch_size": config.data.batch_size,
             "img_scale": config.data.img_scale, "timestamp": datetime.now().isoformat(),
-            "data_parallel_ranks": world}, indent=2))
+            "data_parallel_ranks": world, "distortion_weight": distortion_weight}, indent=2))
         log(f"NeRF training: {exp_name} -> {output_dir} ({world} rank(s), {sampler.n_rays:,} rays, "
             f"{train_data.H}x{train_data.W}, focal {train_data.focal:.2f})")
 
@@ -276,7 +279,8 @@ def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
                                             loss_fine=vm.get("loss_fine"), psnr=psnr, learning_rate=lr,
                                             time_per_iter=batch_time, rays_per_sec=B / batch_time))
         if it % config.train.log_every == 0:
-            log(f"[{it:7d}/{config.train.num_iterations}] loss: {vm['loss']:.5f} | psnr: {psnr:.2f} | "
+            dist_part = f"distortion: {vm['loss_distortion']:.5f} | " if "loss_distortion" in vm else ""
+            log(f"[{it:7d}/{config.train.num_iterations}] loss: {vm['loss']:.5f} | psnr: {psnr:.2f} | {dist_part}"
                 f"lr: {lr:.2e} | rays/s: {B / batch_time:.0f} | time: {(time.time() - start) / 60:.1f}min")
 
     while iteration < config.train.num_iterations:
@@ -303,7 +307,7 @@ def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
                 m = graphed.step(*args)
             else:  # eager (also an epoch's short final batch in graph mode)
                 m = trainer.step(*args)
-            keys = ["loss", "loss_coarse"] + (["loss_fine"] if "loss_fine" in m else [])
+            keys = ["loss", "loss_coarse"] + [k for k in ("loss_fine", "loss_distortion") if k in m]
             now = time.time()
             log_iteration(lagged.push(mean_over_ranks([m[k] for k in keys], process_group),
                                       (iteration, keys, optimizer.param_groups[0]["lr"], now - t_prev)))
@@ -343,7 +347,8 @@ def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
 
 
 def build_arg_parser():
-    """Reference train.py:580-657 flags (same names and defaults) plus ``--precision`` and ``--graph``."""
+    """Reference train.py:580-657 flags (same names and defaults) plus ``--precision``, ``--graph`` and
+    ``--distortion_weight``."""
     import argparse
     ap = argparse.ArgumentParser(description="Train NeRF with optional pose noise (MI355X HIP path)")
     ap.add_argument("--scene", type=str, default="lego")
@@ -371,6 +376,9 @@ def build_arg_parser():
     ap.add_argument("--graph", action="store_true",
                     help="replay the training step from a hipGraph (same results as eager; with RCCL data "
                          "parallelism the all-reduces are captured too)")
+    ap.add_argument("--distortion_weight", type=float, default=0.0,
+                    help="weight of the distortion regulariser on the rendering network's ray weights "
+                         "(mip-NeRF 360; 0 = off, 0.01 is the paper's)")
     return ap
 
 
@@ -399,7 +407,7 @@ def main(argv=None) -> None:
         name = [generate_experiment_name(a.scene, noise_config)]
         dist.broadcast_object_list(name, src=0, group=pg)
         cfg.train.experiment_name = name[0]
-    train(cfg, noise_config, process_group=pg, graph=a.graph)
+    train(cfg, noise_config, process_group=pg, graph=a.graph, distortion_weight=a.distortion_weight)
     if pg is not None:
         import torch.distributed as dist
         dist.destroy_process_group()

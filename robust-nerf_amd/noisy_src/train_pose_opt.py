@@ -354,7 +354,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                  process_group=None, experiment_name: Optional[str] = None,
                                  log=print, graph: bool = False, c2f: Optional[Tuple[float, float]] = None,
                                  fixed_small_angle: bool = False, learn_focal: Optional[str] = None,
-                                 focal_init_scale: float = 1.0) -> Dict[str, object]:
+                                 focal_init_scale: float = 1.0, distortion_weight: float = 0.0) -> Dict[str, object]:
     """Reference train_pose_opt.py:613-1054 (same arguments, outputs and files).
     ``train_data`` / ``val_data`` (optional) replace the on-disk scene; ``process_group``
     makes it data parallel; ``experiment_name`` pins the generated run name (all ranks).
@@ -372,7 +372,10 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     dataset's: same Adam, learning rate, schedule and delay as the poses; validation renders
     use the learned value, the log and train_metrics.csv report its error in per cent
     against the dataset's, checkpoints gain ``intrinsics`` and final_poses.pt the three
-    ``*_focal`` entries.  None (the default) is the reference's fixed focal length."""
+    ``*_focal`` entries.  None (the default) is the reference's fixed focal length.
+    ``distortion_weight`` > 0 (``--distortion_weight``) adds that multiple of the distortion
+    loss on the rendering network's ray weights (``engine.PoseTrainer``); its value goes to
+    the console line only."""
     import torch.distributed as dist
 
     rank, world = 0, 1
@@ -433,7 +436,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     trainer = PoseTrainer(model_coarse, model_fine, camera_params, pixel_sampler, config.render, lr=config.train.lr,
                           pose_lr=pose_lr, lr_decay=config.train.lr_decay, rotation_reg_weight=rotation_reg_weight,
                           translation_reg_weight=translation_reg_weight, process_group=process_group,
-                          pe_schedule=pe_schedule, intrinsics=intrinsics)
+                          pe_schedule=pe_schedule, intrinsics=intrinsics, distortion_weight=distortion_weight)
     optimizer_nerf, optimizer_poses = trainer.optimizer_nerf, trainer.optimizer_poses
     lpips_metric = LPIPSMetric(device=device) if rank == 0 else None
     if lpips_metric is not None and not lpips_metric.available:
@@ -447,6 +450,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
             extra["fixed_small_angle"] = True
         if intrinsics is not None:
             extra["learn_focal"] = {"mode": learn_focal, "focal_init_scale": focal_init_scale}
+        extra["distortion_weight"] = distortion_weight
         (output_dir / "experiment_config.json").write_text(json.dumps({
             "scene": config.data.scene_name, "experiment_name": exp_name, "init_mode": init_mode,
             "pose_optimization": {"learn_rotation": learn_rotation, "learn_translation": learn_translation,
@@ -482,6 +486,8 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                             focal_error_pct=vm.get("focal_error_pct")))
         if it % config.train.log_every == 0:
             focal = f" | focal err: {vm['focal_error_pct']:.3f}%" if "focal_error_pct" in vm else ""
+            if "loss_distortion" in vm:
+                focal += f" | distortion: {vm['loss_distortion']:.5f}"
             log(f"[{it:7d}/{config.train.num_iterations}] loss: {vm['loss']:.5f} | psnr: {psnr:.2f} | "
                 f"lr: {lr:.2e} | poses: {'optimizing' if now else 'frozen'}{focal} | "
                 f"time: {(time.time() - start) / 60:.1f}min")
@@ -506,7 +512,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
             m = graphed.step(*args, iteration=iteration)  # eager once more where the pose Adam's state is new
         else:
             m = trainer.step(*args, iteration=iteration)
-        keys = ["loss", "loss_coarse"] + (["loss_fine"] if "loss_fine" in m else [])
+        keys = ["loss", "loss_coarse"] + [k for k in ("loss_fine", "loss_distortion") if k in m]
         vals = [m[k] for k in keys]
         if intrinsics is not None:  # a device scalar like the losses: read one iteration late
             keys.append("focal_error_pct")
@@ -599,7 +605,8 @@ GRAPH_HELP = ("replay the joint step from hipGraphs, one for frozen poses and on
 
 def build_arg_parser():
     """Reference train_pose_opt.py:1057-1142 flags (same names and defaults) plus ``--precision``,
-    ``--graph``, ``--c2f``, ``--fixed_small_angle``, ``--learn_focal`` and ``--focal_init_scale``."""
+    ``--graph``, ``--c2f``, ``--fixed_small_angle``, ``--learn_focal``, ``--focal_init_scale`` and
+    ``--distortion_weight``."""
     import argparse
     ap = argparse.ArgumentParser(description="Joint NeRF + camera pose optimisation (MI355X HIP path)")
     ap.add_argument("--scene", type=str, default="lego")
@@ -643,6 +650,9 @@ def build_arg_parser():
     ap.add_argument("--focal_init_scale", type=float, default=1.0,
                     help="with --learn_focal: start from this multiple of the dataset's focal length (the "
                          "deterministic counterpart of the pose-noise flags)")
+    ap.add_argument("--distortion_weight", type=float, default=0.0,
+                    help="weight of the distortion regulariser on the rendering network's ray weights "
+                         "(mip-NeRF 360; 0 = off, 0.01 is the paper's)")
     return ap
 
 
@@ -673,7 +683,7 @@ def main(argv=None) -> None:
                                  a.translation_reg_weight, process_group=pg, experiment_name=name[0],
                                  graph=a.graph, c2f=tuple(a.c2f) if a.c2f is not None else None,
                                  fixed_small_angle=a.fixed_small_angle, learn_focal=a.learn_focal,
-                                 focal_init_scale=a.focal_init_scale)
+                                 focal_init_scale=a.focal_init_scale, distortion_weight=a.distortion_weight)
     if pg is not None:
         import torch.distributed as dist
         dist.destroy_process_group()

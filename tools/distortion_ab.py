@@ -1,0 +1,151 @@
+"""The training step without and with the distortion regulariser, and its kernel alone.
+
+Workload: bench.py's flagship (BASELINE cfg #2): 4,096 lego rays per step (bench.lego_rays),
+bf16 networks from seed 42, 64 coarse + 128 fine samples, ``Trainer(coarse_stream="auto")``, the
+randoms drawn per step.  The legs -- w0 (``distortion_weight=0``) and w001 (0.01) -- run in ONE
+process, alternating, REPEATS times each; a run is WARMUP untimed steps, a device sync, STEPS
+timed steps and a device sync.  Each leg trains its own copy of the model.
+
+The json records the three things the step's cost is made of:
+* ``step``: every run's ms/step per leg, medians, and w001 - w0.  With --parent-bench FILE (a
+  bench.py result line of the parent commit from the same box) also w0 against that line's
+  ms_per_step: weight 0 launches nothing new, so the two must agree within the box-to-box
+  spread the README quotes (3 %); ``w0_within_spread`` says whether they do.
+* ``kernel``: ``nr_distortion_loss`` alone at (4096, 192) on the weights and depths of a
+  rendered batch, bracketed by HIP events over CALLS back-to-back launches, against the time
+  of moving its own 12 B per sample (read w, read z, write g_w) at bench.PEAK_HBM_GBS.
+* ``extra_composite_bwd``: the ``nr_composite_bwd`` with ``g_weights`` that a non-zero weight adds
+  to the step (``_CompositeMSE.backward``), timed the same way, plus the elementwise sums that
+  join its gradients to the fused launch's.
+
+python tools/distortion_ab.py [--parent-bench FILE] [--out FILE] [--steps 200] [--warmup 20]
+                              [--repeats 3] [--calls 200]"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+WEIGHT = 0.01
+SPREAD = 0.03  # README: "MI355X boxes differ by about +-3 %"
+
+
+def _events_ms(fn, calls, warmup=20):
+    """Mean ms of ``fn`` over ``calls`` back-to-back launches between two HIP events."""
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / calls
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--parent-bench", type=Path, default=None)
+    ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "distortion_ab.json")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--calls", type=int, default=200)
+    a = ap.parse_args(argv)
+    if a.steps < 200 or a.warmup < 20 or a.repeats < 3:
+        raise SystemExit("distortion_ab: the protocol needs >= 200 timed steps, >= 20 warm-up steps and >= 3 repeats")
+    if not torch.cuda.is_available():
+        raise SystemExit("distortion_ab: no GPU found (this is a measurement on the MI355X; there is no CPU path)")
+    sys.path[:0] = [str(ROOT), str(ROOT / "robust-nerf_amd")]
+
+    import bench
+    from noisy_src import _hip
+    from noisy_src._hip import call, ptr
+    from noisy_src.config import ModelConfig, RenderConfig
+    from noisy_src.engine import Trainer
+    from noisy_src.model import create_nerf
+    from noisy_src.rendering import render_rays
+
+    dev = torch.device("cuda", 0)
+    B, rc = 4096, RenderConfig(num_samples=64, num_samples_fine=128)
+    S = rc.num_samples + rc.num_samples_fine
+    pool = [bench.lego_rays(B, k, dev) for k in range(4)]
+
+    def make_trainer(weight):
+        torch.manual_seed(42)
+        mc, mf = create_nerf(ModelConfig(precision="bf16"))
+        return Trainer(mc.to(dev), mf.to(dev), rc, coarse_stream="auto", distortion_weight=weight)
+
+    def timed(tr):
+        for k in range(a.warmup):
+            tr.step(*pool[k % len(pool)])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(a.steps):
+            tr.step(*pool[k % len(pool)])
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / a.steps
+
+    legs = {"w0": make_trainer(0.0), "w001": make_trainer(WEIGHT)}
+    torch.manual_seed(1234)
+    runs = {name: [] for name in legs}
+    for _ in range(a.repeats):
+        for name, tr in legs.items():  # alternating: every leg sees the same machine state
+            runs[name].append(round(timed(tr), 4))
+    med = {name: sorted(v)[len(v) // 2] for name, v in runs.items()}
+    last = legs["w001"].step(*pool[0])
+    step = {"ms_per_step": runs, "median_ms": med, "spread_ms": {n: round(max(v) - min(v), 4) for n, v in runs.items()},
+            "w001_minus_w0_ms": round(med["w001"] - med["w0"], 4),
+            "final": {k: float(last[k]) for k in ("loss", "loss_fine", "loss_distortion")}}
+    if a.parent_bench is not None:
+        line = [ln for ln in a.parent_bench.read_text().splitlines() if ln.lstrip().startswith("{")][-1]
+        parent_ms = float(json.loads(line)["ms_per_step"])
+        rel = med["w0"] / parent_ms - 1.0
+        step.update(parent_bench_ms=parent_ms, w0_vs_parent=round(rel, 4), w0_within_spread=abs(rel) <= SPREAD)
+
+    # the kernel alone, on the fine weights and depths of a rendered batch
+    with torch.no_grad():
+        mc, mf = legs["w0"].model_coarse, legs["w0"].model_fine
+        _, aux = render_rays(mc, mf, pool[0][0], pool[0][1], rc, is_train=True, return_aux=True)
+    w, z = aux["weights_fine"].contiguous(), aux["z_fine"].contiguous()
+    assert w.shape == (B, S)
+    loss = torch.empty((), device=dev)
+    g_w = torch.empty_like(w)
+    ws = torch.empty(int(_hip.load().nr_distortion_workspace_bytes(B)), device=dev, dtype=torch.uint8)
+    stream = _hip.stream_ptr()
+    k_ms = _events_ms(lambda: call("nr_distortion_loss", ptr(w), ptr(z), B, S, rc.near, rc.far, WEIGHT, ptr(loss), None,
+                                   ptr(g_w), ptr(ws), stream), a.calls)
+    nbytes = 12 * B * S
+    floor_ms = nbytes / (bench.PEAK_HBM_GBS * 1e9) * 1e3
+    kernel = {"B": B, "S": S, "ms": round(k_ms, 5), "bytes": nbytes, "hbm_floor_ms": round(floor_ms, 5),
+              "times_floor": round(k_ms / floor_ms, 2), "GBps": round(nbytes / (k_ms * 1e-3) / 1e9, 1),
+              "loss": float(loss)}
+
+    # the composite backward a non-zero weight adds, and the sums that fold it in
+    g = torch.Generator(device=dev).manual_seed(7)
+    rgb, sigma = torch.rand(B, S, 3, device=dev, generator=g), torch.rand(B, S, device=dev, generator=g) * 3
+    rd = pool[0][1].contiguous()
+    gm = torch.zeros(B, 3, device=dev)
+    e_rgb, e_sigma, e_rd = torch.empty_like(rgb), torch.empty_like(sigma), torch.zeros_like(rd)
+    b_ms = _events_ms(lambda: call("nr_composite_bwd", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), None, B, S, 1, ptr(gm), None,
+                                   None, ptr(g_w), ptr(e_rgb), ptr(e_sigma), ptr(e_rd), stream), a.calls)
+    s_ms = _events_ms(lambda: (rgb + e_rgb, sigma + e_sigma, torch.zeros_like(rd)), a.calls)
+    extra = {"nr_composite_bwd_ms": round(b_ms, 5), "gradient_sums_ms": round(s_ms, 5),
+             "total_ms": round(b_ms + s_ms, 5)}
+
+    doc = {"tool": "tools/distortion_ab.py", "device": torch.cuda.get_device_name(0), "precision": "bf16",
+           "rays": B, "samples": [rc.num_samples, rc.num_samples_fine], "weight": WEIGHT, "steps": a.steps,
+           "warmup": a.warmup, "repeats": a.repeats, "calls": a.calls, "step": step, "kernel": kernel,
+           "extra_composite_bwd": extra}
+    print(json.dumps(doc), flush=True)
+    a.out.parent.mkdir(parents=True, exist_ok=True)
+    a.out.write_text(json.dumps(doc, indent=1) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
