@@ -45,11 +45,14 @@ bool plan_or_error(const NrMlpConfig* cfg, MlpPlan* p) {
     return true;
 }
 
-void add_stream_layer(StreamDesc& sd, int nchunks, int chunk_kb, int load_kb = -1) {
-    for (int c = 0; c < nchunks && sd.nq < kMaxChunks; ++c) {
+// false when the stream would not fit: the caller fails instead of running on a truncated one
+bool add_stream_layer(StreamDesc& sd, int nchunks, int chunk_kb, int load_kb = -1) {
+    if (sd.nq + nchunks > kMaxChunks) return false;
+    for (int c = 0; c < nchunks; ++c) {
         sd.ckb[sd.nq] = load_kb < 0 ? chunk_kb : load_kb;
         sd.cadv[sd.nq++] = chunk_kb;
     }
+    return true;
 }
 
 // 16-bit forward arguments; the saved region's offsets are the caller's (training: make_sizes)
@@ -255,7 +258,8 @@ int nr_mlp_forward(const NrMlpConfig* cfg, const void* packed, const float* para
     a.sd.base = p.lin[0].pk_fwd;
     for (int l = 0; l < p.n_lin; ++l) {
         const LinearDesc& dl = p.lin[l];
-        add_stream_layer(a.sd, dl.KB, dl.NB * p.fpb);
+        NR_REQUIRE(add_stream_layer(a.sd, dl.KB, dl.NB * p.fpb),
+                   "nr_mlp_forward: the weight stream exceeds kMaxChunks = %d chunks", kMaxChunks);
         a.vb[l] = dl.vb;
         a.bo[l] = dl.b_off;
     }
@@ -340,15 +344,17 @@ int nr_mlp_backward_dx(const NrMlpConfig* cfg, const void* packed, const float* 
     b.skips = p.skips;
     // a skip layer's W^T chunk is [h rows | x_enc rows] and dir's is [feat rows |
     // d_enc rows]: without g_x / g_d only the first 8 row blocks are loaded
+    bool stream_fits = true;
     auto add_T = [&](int l) {
         const bool partial = !wx && ((l > 0 && l < n && is_skip(p, l - 1)) || l == n + 1);
-        add_stream_layer(b.sd, p.lin[l].NB, p.lin[l].KB * p.fpb, partial ? kHB * p.fpb : -1);
+        stream_fits &= add_stream_layer(b.sd, p.lin[l].NB, p.lin[l].KB * p.fpb, partial ? kHB * p.fpb : -1);
     };
     b.sd.base = p.lin[n + 1].pk_bwd;
     add_T(n + 1);  // dir^T
     add_T(n);      // feat^T
     for (int i = n - 1; i >= 1; --i) add_T(i);
     if (wx) add_T(0);
+    NR_REQUIRE(stream_fits, "nr_mlp_backward_dx: the weight stream exceeds kMaxChunks = %d chunks", kMaxChunks);
     b.vsig = p.vsig;
     b.vrgb = p.vrgb;
     b.mask_off = z.mask_off;

@@ -203,14 +203,15 @@ int launch_fwd_rbm_t(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
 template <int PREC, bool INPUT = false>
 int launch_bwd_rbm_t(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
     constexpr int W = kRbmWaves;
-    const size_t lds = bwdr_lds_bytes(p.n_mask, W);
-    if (lds > 160 * 1024) {
-        set_error("nr_mlp_backward_dx: %zu bytes of LDS exceed 160 KiB", lds);
-        return NR_EARG;
-    }
+    // the masks of every layer in LDS where they fit (up to 10 trunk layers), else read in place
+    const bool mlds = bwdr_lds_bytes(p.n_mask, W) <= 160 * 1024;
+    const size_t lds = bwdr_lds_bytes(mlds ? p.n_mask : 0, W);
     // every part of every segment (mlp_bwd_rbm_kernel's workgroup mapping)
     const dim3 grid(static_cast<unsigned>(a.nseg * (kSegTiles / W))), block(W * 64);
-    hipLaunchKernelGGL((mlp_bwd_rbm_kernel<PREC, W, INPUT>), grid, block, lds, s, a);
+    if (mlds)
+        hipLaunchKernelGGL((mlp_bwd_rbm_kernel<PREC, W, INPUT, true>), grid, block, lds, s, a);
+    else
+        hipLaunchKernelGGL((mlp_bwd_rbm_kernel<PREC, W, INPUT, false>), grid, block, lds, s, a);
     return check_launch(INPUT ? "nr_mlp_backward_input" : "nr_mlp_backward_dx");
 }
 

@@ -17,7 +17,11 @@
 // runs under the next row block's MFMAs.  Same products in the same k order as
 // the chunk-major 16-bit chain it replaced, to which its dz images were bit-identical.
 // The ReLU masks of every layer are staged into LDS once (LDS-DMA, 1 KB per
-// layer and wave), so no global load waits inside the stream.
+// layer and wave), so no global load waits inside the stream.  That takes 8 KB per
+// masked layer beside the stream's 64 KB: up to 10 trunk layers fit the 160 KiB.  A
+// deeper net runs the MLDS = false instance, which stages none and reads each layer's
+// mask from global memory where the staged form reads LDS (the same words, so the same
+// dz; the load is not counted in s.nvm, which only makes the next stream wait stricter).
 
 constexpr int kBwdrSlot = 32 * 1024;  // every dX-chain chunk: 2 row blocks x 8 k blocks, or 4 x 4
 __host__ __device__ constexpr int bwdr_mask_off() { return 2 * kBwdrSlot; }
@@ -75,7 +79,7 @@ struct BwdrFeatFin {
 // without scratch tiles (a wave without a tile takes tile 0's: its inputs are zero and
 // its stores land in its scratch tile).  s.nvm counts the stores actually issued; which
 // layers store is the same for every wave of the launch.
-template <int PREC, int W, bool INPUT = false>
+template <int PREC, int W, bool INPUT = false, bool MLDS = true>
 __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
     static_assert(kSegTiles % W == 0, "whole parts per segment");
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -101,18 +105,24 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
     // this wave's ReLU masks (n_mask KB) and w_sigma (wave 0) -> LDS; older than the
     // stream's first chunk, so its boundary wait publishes them.  The dir layer's
     // mask (needed before the stream) is also read directly.
-    char* mlds = lds + bwdr_mask_off() + wv * a.n_mask * 1024;
+    const int nml = MLDS ? a.n_mask : 0;  // mask KB per wave in LDS (launch_bwd_rbm_t sizes it the same way)
+    char* mlds = lds + bwdr_mask_off() + wv * nml * 1024;
     const char* msrc = a.saved + a.mask_off + (INPUT && !ts.live ? 0 : tile) * a.n_mask * 1024;
-    for (int l = 0; l < a.n_mask; ++l)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(msrc + l * 1024 + lane16()),
-                                         (__attribute__((address_space(3))) void*)(mlds + l * 1024), 16, 0, 0);
+    if constexpr (MLDS)
+        for (int l = 0; l < a.n_mask; ++l)
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) void*)(msrc + l * 1024 + lane16()),
+                (__attribute__((address_space(3))) void*)(mlds + l * 1024), 16, 0, 0);
     if (wv == 0)
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) void*)(a.packed + a.vhead + lane16()),
-            (__attribute__((address_space(3))) void*)(lds + bwdr_sig_off(a.n_mask, W)), 16, 0, 0);
+            (__attribute__((address_space(3))) void*)(lds + bwdr_sig_off(nml, W)), 16, 0, 0);
     const u32x4 mwc = *reinterpret_cast<const u32x4*>(msrc + n * 1024 + lane16());
-    auto mask_of = [&](int layer) { return *reinterpret_cast<const u32x4*>(mlds + layer * 1024 + lane16()); };
-    const float* wsig = reinterpret_cast<const float*>(lds + bwdr_sig_off(a.n_mask, W)) + 16 * h;
+    auto mask_of = [&](int layer) {
+        if constexpr (MLDS) return *reinterpret_cast<const u32x4*>(mlds + layer * 1024 + lane16());
+        else return *reinterpret_cast<const u32x4*>(msrc + layer * 1024 + lane16());
+    };
+    const float* wsig = reinterpret_cast<const float*>(lds + bwdr_sig_off(nml, W)) + 16 * h;
 
     RStream s{lds, a.packed + a.base, -1, 0, wv, kBwdrSlot, W};
     constexpr int CK_DIR = rbm_chunk_kb(NC, 0), CK_H = rbm_chunk_kb(kHB, 0);

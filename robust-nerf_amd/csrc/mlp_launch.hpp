@@ -16,9 +16,7 @@ inline float grad_scale(int prec) { return prec == NR_PREC_FP16 ? 16384.0f : 1.0
 
 // ------------------------------------------- fp32, chunk-major (mlp_fp32.hip) ----
 // The weight stream: a sequence of chunks (all row blocks of one k block of one layer
-// image) consumed in order.
-constexpr int kMaxChunks = 176;  // >= sum of KB (forward) or NB (backward) over the MFMA layers
-
+// image) consumed in order; at most kMaxChunks of them (mlp_plan.hpp).
 struct StreamDesc {
     int64_t base;                  // byte offset of the stream's first chunk in `packed`
     int nq;                        // chunks

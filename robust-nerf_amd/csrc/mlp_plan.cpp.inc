@@ -45,7 +45,7 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
     p->dir_dim = 3 * (1 + 2 * p->Ld);
     p->XB = blocks_of(p->pos_dim);
     p->DB = p->use_vd ? blocks_of(p->dir_dim) : 0;
-    if (p->XB > 2 || p->DB > 1) {
+    if (p->XB > 2 || blocks_of(p->dir_dim) > 1) {  // dir_freqs also when use_view_dirs is off: one envelope
         *why = "pos_freqs <= 10 and dir_freqs <= 4 are supported by the compiled kernels";
         return false;
     }
@@ -282,7 +282,9 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
         add_waves(jdir, kHB / 2, kHB / 2 + 1, kHB + DBu, kHB + DBu + kHB / 2, true);  // dz_heads x h_c
     }
     if (!fits) {
-        *why = "dW job shares exceed the 8-wave workgroup";
+        // x-jobs hold two x_enc-reading layers each: n + ceil((skips + 1) / 2) <= 23 (fp32: 22)
+        *why = "dW job shares exceed the 8-wave workgroup (too many skips for this depth: num_hidden_layers + "
+               "ceil((len(skips) + 1) / 2) must not exceed 23, or 22 in fp32)";
         return false;
     }
     int red = 0;

@@ -32,6 +32,10 @@ constexpr int kMaxJobs = kMaxTrunk + 8;  // dW jobs: x-jobs + trunk h-jobs + fea
 constexpr int kMaxSeg = 2;
 constexpr int kMaxJobSeg = 4;            // tensors on either side of a dW job
 constexpr int kMaxRed = kMaxTrunk + 4;    // reduce ranges: trunk, feat, sigma, rgb, dir
+// fp32 weight streams (StreamDesc, mlp_launch.hpp): chunks per stream, >= the sum of KB
+// (forward) or NB (backward) over the MFMA layers of every config make_plan accepts
+// (tests/native/plan_check.cpp sweeps it; the entry points refuse a stream that does not fit)
+constexpr int kMaxChunks = 176;
 // dW staging: each of the 8 waves issues at most this many 1-KB LDS-DMA pieces
 // per tile, so a job's (NBz + KB) * FPB blocks must not exceed 8x it
 __host__ __device__ constexpr int dw_max_pieces(bool k16) { return k16 ? 6 : 10; }
@@ -132,6 +136,20 @@ struct MlpPlan {
 };
 
 inline bool is_skip(const MlpPlan& p, int i) { return (p.skips >> i) & 1u; }
+
+// Chunks of the fp32 weight streams as the entry points build them: the forward streams
+// every k block of every W image, the backward (with input gradients) every row block of
+// every W^T image.
+inline int fwd_stream_chunks(const MlpPlan& p) {
+    int n = 0;
+    for (int l = 0; l < p.n_lin; ++l) n += p.lin[l].KB;
+    return n;
+}
+inline int bwd_stream_chunks(const MlpPlan& p) {
+    int n = 0;
+    for (int l = 0; l < p.n_lin; ++l) n += p.lin[l].NB;
+    return n;
+}
 
 // Builds the plan; returns false (with *why set) for unsupported configs.
 bool make_plan(const NrMlpConfig* cfg, MlpPlan* p, const char** why);

@@ -270,8 +270,11 @@ def _check_supported(cfg: NrMlpConfig, config: ModelConfig, n_params: int) -> No
     """Fail at construction, not at the first forward, for a ModelConfig the compiled
     kernels do not cover.  The fused MLP (csrc/mlp.hip) is specialised for the
     reference's width: hidden_dim 256 (8 MFMA row blocks of 32), pos_freqs <= 10
-    (x_enc in 2 k-blocks), dir_freqs <= 4 (d_enc in 1 k-block); any depth 1..16 and
-    any skip set.  The plan check is host code (nr_mlp_packed_bytes), so this runs
+    (x_enc in 2 k-blocks), dir_freqs <= 4 (d_enc in 1 k-block; also required when
+    use_view_dirs is off, where it used to be ignored: one envelope for both settings); depth 1..16 and
+    skips at layers 0..depth-2, as many as the dW job table holds: depth +
+    ceil((len(skips) + 1) / 2) <= 23 (22 in fp32), which only bites at depths 15 and 16
+    (tests/test_plan.py sweeps it).  The plan check is host code (nr_mlp_packed_bytes), so this runs
     without a GPU."""
     lib = _hip.load()
     if int(lib.nr_mlp_packed_bytes(ctypes.byref(cfg))) < 0:
@@ -279,7 +282,8 @@ def _check_supported(cfg: NrMlpConfig, config: ModelConfig, n_params: int) -> No
             f"ModelConfig(hidden_dim={config.hidden_dim}, pos_freqs={config.pos_freqs}, "
             f"dir_freqs={config.dir_freqs}, num_hidden_layers={config.num_hidden_layers}, skips={config.skips}) "
             f"is outside the envelope of the compiled MI355X kernels: {_hip.last_error()} "
-            "(supported: hidden_dim=256, pos_freqs<=10, dir_freqs<=4, 1..16 layers, any skips)")
+            "(supported: hidden_dim=256, pos_freqs<=10, dir_freqs<=4 with or without view directions, 1..16 layers, skips within "
+            "0..num_hidden_layers-2 with num_hidden_layers + ceil((len(skips)+1)/2) <= 23, or 22 in fp32)")
     want = int(lib.nr_mlp_param_count(ctypes.byref(cfg)))
     if want != n_params:
         raise RuntimeError(f"NeRF parameter layout mismatch: module {n_params} vs kernel plan {want}")

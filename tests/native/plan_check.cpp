@@ -2,6 +2,7 @@
 // every parameter's gradient is read by the dW reduction from a slab entry that
 // exactly one dW wave share writes, and every share stays inside its job's grid.
 //   plan_check pos_freqs dir_freqs n_layers skip_mask use_view_dirs precision
+//   plan_check --sweep     the same checks, in this one process, over the whole config space
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,67 +15,160 @@ static int ceil_div(int a, int b) { return (a + b - 1) / b; }
 }
 #include "mlp_plan.cpp.inc"
 using namespace nr;
-int main(int argc, char** argv) {
-    NrMlpConfig c{10, 4, 256, 8, 1u << 4, 1, 1};
-    if (argc == 7) c = {atoi(argv[1]), atoi(argv[2]), 256, atoi(argv[3]), (uint32_t)atoi(argv[4]), atoi(argv[5]), atoi(argv[6])};
-    MlpPlan p; const char* why = "";
-    if (!make_plan(&c, &p, &why)) { printf("plan fail %s\n", why); return 1; }
-    std::set<std::tuple<int,int,int>> written;  // job,row,col
+
+// The checks of one accepted plan; prints the layout when `say`.  Returns 0 when good.
+static int check_plan(const MlpPlan& p, bool say) {
+#define SAY(...) do { if (say) printf(__VA_ARGS__); } while (0)
+    if (p.n_jobs > kMaxJobs || p.n_red > kMaxRed) { printf("job or reduce table overrun\n"); return 1; }
+    // the fp32 weight streams of nr_mlp_forward / nr_mlp_backward_dx (with input gradients)
+    if (fwd_stream_chunks(p) > kMaxChunks || bwd_stream_chunks(p) > kMaxChunks) { printf("weight stream overrun\n"); return 1; }
+    // shares write whole 32 x 32 blocks (and a 32-row piece of the bias column, block
+    // column KB), so the bookkeeping is per block: writes[job][block row][block column]
+    static std::vector<uint8_t> writes[kMaxJobs];
+    auto at = [&](int j, int br, int bc) -> uint8_t& { return writes[j][br * (p.job[j].KB + 1) + bc]; };
+    auto once = [&](int j, int row, int col) {  // slab entry (row, col) of job j: written exactly once?
+        if (j < 0 || j >= p.n_jobs || row < 0 || col < 0 || row >= p.job[j].NBz * 32 || col > p.job[j].KB * 32) return false;
+        return at(j, row / 32, col / 32) == 1;
+    };
     long dup = 0;
     for (int j = 0; j < p.n_jobs; ++j) {
         const DwJob& jb = p.job[j];
-        printf("job %d NBz %d KB %d waves %d:", j, jb.NBz, jb.KB, jb.nwaves);
+        if (jb.NBz < 0 || jb.KB < 0 || jb.NBz >= 64 || jb.KB >= 64) { printf("job grid beyond the wave pack\n"); return 1; }
+        writes[j].assign(jb.NBz * (jb.KB + 1), 0);
+    }
+    for (int j = 0; j < p.n_jobs; ++j) {
+        const DwJob& jb = p.job[j];
+        SAY("job %d NBz %d KB %d waves %d:", j, jb.NBz, jb.KB, jb.nwaves);
         // the dW kernel stages at most dw_max_pieces 1-KB pieces per wave and tile
         if ((jb.NBz + jb.KB) * p.fpb > kDwMaxWaves * dw_max_pieces(p.fpb == 2)) {
             printf("\nstaging exceeds the per-wave pieces\n");
             return 1;
         }
+        if (jb.nwaves > kDwMaxWaves || jb.ndz > kMaxJobSeg || jb.nin > kMaxJobSeg) { printf("\njob overrun\n"); return 1; }
         for (int v = 0; v < jb.nwaves; ++v) {
             const DwWave& w = jb.w[v];
-            printf(" [%d+%d x %d+%d%s]", w.row0, w.np, w.col0, w.nq, w.bias ? " b" : "");
-            if (w.np < 1 || w.np > kDwMaxP || w.nq < 1 || w.nq > kDwMaxQ || w.row0 + w.np > jb.NBz ||
-                w.col0 + w.nq > jb.KB) { printf("\nshare out of grid\n"); return 1; }
-            for (int r = 32 * w.row0; r < 32 * (w.row0 + w.np); ++r) {
-                for (int cc = 32 * w.col0; cc < 32 * (w.col0 + w.nq); ++cc) dup += !written.insert({j, r, cc}).second;
-                if (w.bias) dup += !written.insert({j, r, jb.KB * 32}).second;
+            SAY(" [%d+%d x %d+%d%s]", w.row0, w.np, w.col0, w.nq, w.bias ? " b" : "");
+            if (w.np < 1 || w.np > kDwMaxP || w.nq < 1 || w.nq > kDwMaxQ || w.row0 < 0 || w.col0 < 0 ||
+                w.row0 + w.np > jb.NBz || w.col0 + w.nq > jb.KB) { printf("\nshare out of grid\n"); return 1; }
+            for (int br = w.row0; br < w.row0 + w.np; ++br) {
+                for (int bc = w.col0; bc < w.col0 + w.nq; ++bc) dup += 1024L * (++at(j, br, bc) > 1);
+                if (w.bias) dup += 32L * (++at(j, br, jb.KB) > 1);
             }
         }
-        printf("\n");
+        SAY("\n");
     }
+    // every parameter the reduction reads: the rows of a range x the columns of the one
+    // segment that holds each column (walked in 32-wide steps: a block is written whole)
     long bad = 0, n = 0;
     for (int k = 0; k < p.n_red; ++k) {
         const ReduceRange& r = p.red[k];
-        for (int row = 0; row < r.rows; ++row) {
-            for (int col = 0; col < r.in; ++col) {
-                int job = -1, sr = 0, sc = 0;
-                for (int s = 0; s < r.nseg; ++s) {
-                    const RedSeg& sg = r.seg[s];
-                    if (col >= sg.col0 && col < sg.col0 + sg.width) { job = sg.job; sr = sg.slab_row0 + row; sc = sg.slab_col0 + col - sg.col0; }
+        if (r.nseg < 1 || r.nseg > kMaxSeg) { printf("reduce range %d has %d segments\n", k, r.nseg); return 1; }
+        std::vector<int> owners(r.in, 0);
+        for (int s = 0; s < r.nseg; ++s) {
+            const RedSeg& sg = r.seg[s];
+            if (sg.col0 < 0 || sg.width < 1 || sg.col0 + sg.width > r.in) { printf("reduce range %d segment %d out of range\n", k, s); return 1; }
+            for (int col = sg.col0; col < sg.col0 + sg.width; ++col) ++owners[col];
+            if (sg.slab_row0 < 0 || sg.slab_col0 < 0) { printf("reduce range %d segment %d: negative slab origin\n", k, s); return 1; }
+            for (int row = 0, rstep; row < r.rows; row += rstep) {
+                const int sr = sg.slab_row0 + row;
+                rstep = 32 - sr % 32 < r.rows - row ? 32 - sr % 32 : r.rows - row;
+                for (int col = 0, step; col < sg.width; col += step) {
+                    const int sc = sg.slab_col0 + col;
+                    step = 32 - sc % 32 < sg.width - col ? 32 - sc % 32 : sg.width - col;
+                    n += long(rstep) * step;
+                    if (!once(sg.job, sr, sc) || sc >= p.job[sg.job].KB * 32) { if (bad < 5) printf("unwritten W red %d row %d col %d job %d (%d,%d)\n", k, row, sg.col0 + col, sg.job, sr, sc); bad += long(rstep) * step; }
                 }
-                ++n;
-                if (job < 0 || !written.count({job, sr, sc})) { if (bad < 5) printf("unwritten W red %d row %d col %d job %d (%d,%d)\n", k, row, col, job, sr, sc); ++bad; }
             }
+        }
+        for (int col = 0; col < r.in; ++col)
+            if (owners[col] != 1) { if (bad < 5) printf("red %d col %d in %d segments\n", k, col, owners[col]); ++bad; }
+        for (int row = 0; row < r.rows; ++row) {
             ++n;
-            if (!written.count({r.bjob, r.brow0 + row, p.job[r.bjob].KB * 32})) { if (bad < 10) printf("unwritten b red %d row %d\n", k, row); ++bad; }
+            if (r.bjob < 0 || r.bjob >= p.n_jobs || !once(r.bjob, r.brow0 + row, p.job[r.bjob].KB * 32)) { if (bad < 10) printf("unwritten b red %d row %d\n", k, row); ++bad; }
         }
     }
-    printf("params %ld (plan %ld) unwritten %ld doubly written %ld\n", n, (long)p.param_count, bad, dup);
+    SAY("params %ld (plan %ld) unwritten %ld doubly written %ld\n", n, (long)p.param_count, bad, dup);
     // dW workgroups per job (make_sizes): one round, every job at least one chunk, the
     // slab sets cover the largest job; uniform for 16-bit (the pipelined backward's chunks)
     long wg_bad = 0;
     for (long M : {1L, 5000L, 262144L, 786432L}) {
         const MlpSizes z = make_sizes(p, M);
         int tot = 0, mx = 0;
-        printf("M %ld chunks %d max %d:", M, z.chunks, z.max_chunks);
+        SAY("M %ld chunks %d max %d:", M, z.chunks, z.max_chunks);
         for (int j = 0; j < p.n_jobs; ++j) {
-            printf(" %d", z.job_chunks[j]);
+            SAY(" %d", z.job_chunks[j]);
             tot += z.job_chunks[j];
             mx = z.job_chunks[j] > mx ? z.job_chunks[j] : mx;
             wg_bad += z.job_chunks[j] < 1 || (p.fpb == 2 && z.job_chunks[j] != z.chunks);
         }
-        printf(" (sum %d)\n", tot);
+        SAY(" (sum %d)\n", tot);
         wg_bad += tot > 256 || mx != z.max_chunks;
     }
-    printf("dW workgroup plan bad %ld\n", wg_bad);
+    SAY("dW workgroup plan bad %ld\n", wg_bad);
+#undef SAY
     return bad != 0 || dup != 0 || n != p.param_count || wg_bad != 0;
+}
+
+// pos_freqs 0..11, dir_freqs 0..5, depth 0..17, both view-direction settings, the three
+// precisions; per depth n the skip masks: none, every single skip, every adjacent pair, the
+// two every-other masks, a skip after every layer, every pair (i, n-2), and every mask
+// with a bit at n-1 or above (singles up to bit 17, and the lowest of them beside skip 0).
+// A config is `valid` when the stated envelope holds it (pos <= 10, dir <= 4, depth
+// 1..16, skips below n-1); a refused valid config is printed, to be compared with what
+// the refusal messages claim.
+static int sweep() {
+    long total = 0, accepted = 0, refused_invalid = 0, refused_valid = 0, failures = 0;
+    int max_jobs = 0, max_red = 0, max_fwd = 0, max_bwd = 0;
+    for (int n = 0; n <= kMaxTrunk + 1; ++n) {
+        std::set<uint32_t> masks{0};
+        const uint32_t all = n >= 2 ? (1u << (n - 1)) - 1 : 0;
+        for (int i = 0; i + 1 < n; ++i) {
+            masks.insert(1u << i);
+            if (i + 2 < n) masks.insert(3u << i);
+            if (n >= 2) masks.insert((1u << i) | (1u << (n - 2)));
+        }
+        masks.insert(all & 0x55555555u);
+        masks.insert(all & 0xAAAAAAAAu);
+        masks.insert(all);
+        const int top = n > 0 ? n - 1 : 0;
+        for (int b = top; b <= kMaxTrunk + 1; ++b) masks.insert(1u << b);
+        if (n >= 2) masks.insert(1u | (1u << top));
+        for (uint32_t mask : masks)
+            for (int L = 0; L <= 11; ++L)
+                for (int Ld = 0; Ld <= 5; ++Ld)
+                    for (int vd = 0; vd <= 1; ++vd)
+                        for (int prec : {NR_PREC_FP32, NR_PREC_BF16, NR_PREC_FP16}) {
+                            NrMlpConfig c{L, Ld, 256, n, mask, vd, prec};
+                            const bool valid = L <= 10 && Ld <= 4 && n >= 1 && n <= kMaxTrunk && (mask >> top) == 0;
+                            MlpPlan p;
+                            const char* why = "";
+                            ++total;
+                            if (!make_plan(&c, &p, &why)) {
+                                if (!why || !*why) { printf("FAIL empty reason %d %d %d %u %d %d\n", L, Ld, n, mask, vd, prec); ++failures; }
+                                if (valid) { printf("refused %d %d %d %u %d %d: %s\n", L, Ld, n, mask, vd, prec, why); ++refused_valid; }
+                                else ++refused_invalid;
+                                continue;
+                            }
+                            ++accepted;
+                            if (!valid || check_plan(p, false)) { printf("FAIL %s %d %d %d %u %d %d\n", valid ? "check" : "accepted invalid", L, Ld, n, mask, vd, prec); ++failures; }
+                            max_jobs = p.n_jobs > max_jobs ? p.n_jobs : max_jobs;
+                            max_red = p.n_red > max_red ? p.n_red : max_red;
+                            max_fwd = fwd_stream_chunks(p) > max_fwd ? fwd_stream_chunks(p) : max_fwd;
+                            max_bwd = bwd_stream_chunks(p) > max_bwd ? bwd_stream_chunks(p) : max_bwd;
+                        }
+    }
+    printf("sweep total %ld accepted %ld refused_valid %ld refused_invalid %ld failures %ld\n", total, accepted,
+           refused_valid, refused_invalid, failures);
+    printf("sweep max n_jobs %d of %d n_red %d of %d fwd_chunks %d bwd_chunks %d of %d\n", max_jobs, kMaxJobs, max_red,
+           kMaxRed, max_fwd, max_bwd, kMaxChunks);
+    return failures != 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 2 && !strcmp(argv[1], "--sweep")) return sweep();
+    NrMlpConfig c{10, 4, 256, 8, 1u << 4, 1, 1};
+    if (argc == 7) c = {atoi(argv[1]), atoi(argv[2]), 256, atoi(argv[3]), (uint32_t)atoi(argv[4]), atoi(argv[5]), atoi(argv[6])};
+    MlpPlan p; const char* why = "";
+    if (!make_plan(&c, &p, &why)) { printf("plan fail %s\n", why); return 1; }
+    return check_plan(p, true);
 }

@@ -49,10 +49,11 @@ CONFIGS = {
 
 @functools.lru_cache(maxsize=None)
 def _net(precision, config="default"):
-    """(oracle, HIP network with its weights, packed images) of a named config."""
+    """(oracle, HIP network with its weights, packed images) of a named config (of CONFIGS,
+    or of edge_inputs.CONFIG_CASES for test_mlp_configs.py)."""
     from noisy_src.config import ModelConfig
     from noisy_src.model import NeRF
-    mc = ModelConfig(precision=precision, **CONFIGS[config])
+    mc = ModelConfig(precision=precision, **(CONFIGS[config] if config in CONFIGS else ei.CONFIG_CASES[config][0]))
     torch.manual_seed(0)
     oracle = ref.NeRF(mc)
     net = NeRF(mc)

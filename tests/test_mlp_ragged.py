@@ -49,12 +49,12 @@ GUARD = 33  # sentinel rows behind every per-sample output: more than a tile
 
 
 @functools.lru_cache(maxsize=None)
-def _net(precision):
-    """(oracle, HIP network with the oracle's weights, its packed weight images)."""
-    from noisy_src.config import ModelConfig
+def _net(precision, case=None):
+    """(oracle, HIP network with the oracle's weights, its packed weight images); ``case``
+    names a config of edge_inputs.CONFIG_CASES, None is the default model."""
     from noisy_src.model import NeRF
-    oracle = ei.oracle_net(precision)
-    net = NeRF(ModelConfig(precision=precision))
+    oracle = ei.oracle_net(precision, case=case)
+    net = NeRF(ei.case_config(precision, case))
     net.load_state_dict(oracle.state_dict())
     net = net.to(DEV)
     net._ensure_flat()
@@ -69,13 +69,14 @@ def _same_bits(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
-def mlp_raw(precision, M, x, d, g_rgb, g_sigma, *, rgb, sigma, saved, workspace, g_x, g_d, g_params, dense):
+def mlp_raw(precision, M, x, d, g_rgb, g_sigma, *, rgb, sigma, saved, workspace, g_x, g_d, g_params, dense,
+            case=None):
     """The forward and the split backward on caller-supplied buffers, as
     noisy_src.model._MLPFunction runs them.  Returns the active-tile count the dX launch
     left in the workspace."""
     from noisy_src import _hip
     from noisy_src._hip import call, ptr
-    _, net, packed = _net(precision)
+    _, net, packed = _net(precision, case)
     cfg = _hip.NrMlpConfig.from_buffer_copy(net._nr_cfg)
     cfg.dense_backward = int(dense)
     c, st, flat = ctypes.byref(cfg), _hip.stream_ptr(), net._flat
@@ -90,11 +91,12 @@ def mlp_raw(precision, M, x, d, g_rgb, g_sigma, *, rgb, sigma, saved, workspace,
     return int(workspace[off:off + 4].view(torch.int32).item())
 
 
-def _run(precision, M, x, d, g_rgb, g_sigma, *, tail=0.0, poison=False, dense=1, want_in=True):
+def _run(precision, M, x, d, g_rgb, g_sigma, *, tail=0.0, poison=False, dense=1, want_in=True, case=None):
     """One forward + backward of the first M rows of the inputs.  The input buffers are
-    padded to whole tiles with ``tail`` behind row M; outputs have GUARD sentinel rows."""
+    padded to whole tiles with ``tail`` behind row M; outputs have GUARD sentinel rows.
+    A config without view directions has no g_d."""
     from noisy_src import _hip
-    _, net, _ = _net(precision)
+    _, net, _ = _net(precision, case)
     cfg = ctypes.byref(net._nr_cfg)
     Mp = (M + 31) // 32 * 32
 
@@ -108,11 +110,13 @@ def _run(precision, M, x, d, g_rgb, g_sigma, *, tail=0.0, poison=False, dense=1,
     ws = fill(_hip.load().nr_mlp_workspace_bytes(cfg, M))
     o = dict(rgb=guarded((M, 3), GUARD), sigma=guarded((M,), GUARD), g_params=guarded((net._param_count,), 64))
     if want_in:
-        o.update(g_x=guarded((M, 3), GUARD), g_d=guarded((M, 3), GUARD))
+        o.update(g_x=guarded((M, 3), GUARD))
+        if net.config.use_view_dirs:
+            o.update(g_d=guarded((M, 3), GUARD))
     count = mlp_raw(precision, M, padded(x, 3), padded(d, 3), padded(g_rgb, 3), padded(g_sigma, 1),
                     rgb=o["rgb"].buf, sigma=o["sigma"].buf, saved=saved, workspace=ws,
-                    g_x=o["g_x"].buf if want_in else None, g_d=o["g_d"].buf if want_in else None,
-                    g_params=o["g_params"].buf, dense=dense)
+                    g_x=o["g_x"].buf if want_in else None, g_d=o["g_d"].buf if "g_d" in o else None,
+                    g_params=o["g_params"].buf, dense=dense, case=case)
     torch.cuda.synchronize()
     for v in o.values():
         v.check()  # nothing written behind row M

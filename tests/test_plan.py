@@ -43,3 +43,60 @@ def test_too_many_dw_jobs_fails_cleanly(plan_check):
     hold -- the plan refuses the config instead of overrunning its job table."""
     r = subprocess.run([str(plan_check), "10", "4", "16", str((1 << 15) - 1), "1", "1"], capture_output=True, text=True)
     assert r.returncode != 0 and "plan fail" in r.stdout, r.stdout
+
+
+def _sweep_masks(n):
+    """plan_check.cpp's valid skip masks at depth n (those below bit n - 1)."""
+    full = (1 << (n - 1)) - 1 if n >= 2 else 0
+    masks = {0, full & 0x55555555, full & 0xAAAAAAAA, full}
+    for i in range(n - 1):
+        masks.add(1 << i)
+        masks.add((1 << i) | (1 << (n - 2)))
+        if i + 2 < n:
+            masks.add(3 << i)
+    return masks
+
+
+def test_sweep_of_the_whole_config_space(plan_check):
+    """``plan_check --sweep`` in one process: pos_freqs 0..11, dir_freqs 0..5, depth 0..17,
+    both view-direction settings, three precisions and per depth the skip masks none /
+    singles / adjacent pairs / every other / all / pairs with n-2 / bits at n-1 and above.
+    Every accepted config passes the single-config checks (each gradient written once,
+    shares inside their grids and the staging limit, a good workgroup plan) with its job,
+    reduce and fp32 weight-stream tables inside kMaxJobs / kMaxRed / kMaxChunks; every
+    refusal has a reason; nothing outside the stated envelope is accepted; and the refused
+    configs inside it are exactly those the refusal message names: num_hidden_layers +
+    ceil((len(skips) + 1) / 2) > 23 (22 in fp32), here the all-skips masks at depth 16 and,
+    in fp32, depth 15."""
+    import time
+    t0 = time.perf_counter()
+    r = subprocess.run([str(plan_check), "--sweep"], capture_output=True, text=True)
+    dt = time.perf_counter() - t0
+    lines = r.stdout.splitlines()
+    print(f"PLAN_SWEEP seconds {dt:.1f}: {lines[-2]}; {lines[-1]}")
+    assert r.returncode == 0 and not [ln for ln in lines if ln.startswith("FAIL")], "\n".join(lines[-20:])
+    want = set()
+    n_valid = 0
+    for n in range(1, 17):
+        for mask in _sweep_masks(n):
+            for prec in (0, 1, 2):
+                limit = 22 if prec == 0 else 23
+                for pos in range(11):
+                    for dirf in range(5):
+                        for vd in (0, 1):
+                            n_valid += 1
+                            if n + (bin(mask).count("1") + 2) // 2 > limit:
+                                want.add((pos, dirf, n, mask, vd, prec))
+    got = set()
+    for ln in lines:
+        if ln.startswith("refused "):
+            cfg, why = ln[len("refused "):].split(":", 1)
+            assert "dW job shares exceed the 8-wave workgroup" in why and "23, or 22 in fp32" in why, ln
+            got.add(tuple(map(int, cfg.split())))
+    assert got == want and len(want) == 440
+    assert {(n, m, p) for _, _, n, m, _, p in want} == {(16, 0x7FFF, 0), (16, 0x7FFF, 1), (16, 0x7FFF, 2),
+                                                         (15, 0x3FFF, 0)}
+    tot = dict(zip(lines[-2].split()[1::2], map(int, lines[-2].split()[2::2])))
+    assert tot["failures"] == 0 and tot["refused_valid"] == 440 and tot["accepted"] == n_valid - 440
+    assert tot["total"] == tot["accepted"] + tot["refused_valid"] + tot["refused_invalid"]
+    assert lines[-1] == "sweep max n_jobs 24 of 24 n_red 20 of 20 fwd_chunks 159 bwd_chunks 140 of 176"
