@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from .config import ModelConfig, RenderConfig
+from .logger import depth_to_colormap  # the reference's inference.py:114-125 is its logger.py:290-302
 from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim, image_metrics
 from .model import NeRF
 from .noise import NoiseConfig, add_noise_to_pose, compute_pose_error, set_noise_seed
@@ -104,14 +105,6 @@ def save_image(img: torch.Tensor, path: Path) -> None:
     from PIL import Image
     arr = (img.detach().cpu().numpy() * 255).clip(0, 255).astype(np.uint8)
     Image.fromarray(arr).save(path)
-
-
-def depth_to_colormap(depth: torch.Tensor) -> torch.Tensor:
-    """Reference inference.py:114-125: min-max normalised depth through a turbo-like ramp."""
-    depth = depth.detach().cpu()
-    n = (depth - depth.min()) / (depth.max() - depth.min() + 1e-8)
-    return torch.stack([torch.clamp(4 * n - 1.5, 0, 1), torch.clamp(2 - 4 * torch.abs(n - 0.5), 0, 1),
-                        torch.clamp(1.5 - 4 * n, 0, 1)], dim=-1)
 
 
 def frame_u8(img: torch.Tensor, out: Optional[torch.Tensor] = None, x0: int = 0) -> torch.Tensor:

@@ -16,7 +16,8 @@ Joint NeRF + camera-pose training step — drop-in for ShawnnnLiu/Robust-NeRF
   Adam and its LambdaLR only after ``pose_opt_delay``, one CSV row per iteration,
   validation + pose errors + checkpoint every ``val_every``, checkpoints every
   ``save_every``, the final evaluation and checkpoint, ``final_poses.pt`` and
-  ``summary.json``.  The step is ``engine.PoseTrainer`` (HIP, no host syncs).  Under
+  ``summary.json``.  The step is ``engine.PoseTrainer`` (HIP, no host syncs); what the
+  loop shares with ``train.train`` around the step is ``run``'s.  Under
   ``torchrun`` it is data parallel exactly like ``train.train``: identical global draws
   on every rank, contiguous slices, network and pose gradients averaged over RCCL.
   ``graph=True`` (``--graph``) replays the step from hipGraphs after iteration 0
@@ -37,10 +38,7 @@ Joint NeRF + camera-pose training step — drop-in for ShawnnnLiu/Robust-NeRF
 
 from __future__ import annotations
 
-import json
 import math
-import random
-import time
 from datetime import datetime
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
@@ -54,24 +52,17 @@ from .config import RenderConfig
 from .config import NeRFConfig
 from .data import BlenderData, load_blender_data
 from .data_pose_opt import PixelBatch, PixelSampler, create_pixel_dataset
-from .engine import (GraphedPoseTrainer, LaggedScalars, PoseTrainer, check_run_args, init_distributed,
-                     mean_over_ranks, rank_slice)
-from .logger import ExperimentLogger, TrainingMetrics, ValidationMetrics
-from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim
+from .engine import GraphedPoseTrainer, PoseTrainer
+from .logger import ExperimentLogger, ValidationMetrics
+from .metrics import compute_psnr
 from .model import NeRF
 from .noise import NoiseConfig, add_noise_to_poses, compute_pose_error
 from .optim import FusedAdam, clip_grad_norm_
 from .rendering import NeRFRenderer, render_rays
+from .run import (IterationLog, add_common_args, base_checkpoint, create_nerf_for, draw_randoms, due,  # noqa: F401
+                  evaluate_views, open_run, run_cli, set_seed, slice_for_rank, write_checkpoint,
+                  write_experiment_config)
 from .train import render_image
-
-
-def set_seed(seed: int) -> None:
-    """Reference train_pose_opt.py:44-50."""
-    random.seed(seed)
-    np.random.seed(seed)
-    torch.manual_seed(seed)
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed_all(seed)
 
 
 def pe_window_weights(alpha: float, num_freqs: int) -> List[float]:
@@ -284,24 +275,11 @@ def evaluate_with_poses(model_coarse: NeRF, model_fine: Optional[NeRF], camera_p
     PNGs of the first three when a logger is given.  The networks render with their
     current positional-encoding windows (``NeRF.set_pe_window``), and with the learned
     focal lengths ``fxy`` when given (the field was fitted to rays of that focal length)."""
-    psnr, ssim, mse, lp = [], [], [], []
-    for i, idx in enumerate(val_indices[:min(num_images, len(val_indices))]):
-        idx = int(idx)
-        out = render_image_with_pose(model_coarse, model_fine, val_data.poses[idx], val_data.H, val_data.W,
-                                     val_data.focal, render_config, fxy=fxy)
-        pred, target = out["rgb"], val_data.images[idx]
-        mse.append(compute_mse(pred, target).item())
-        psnr.append(compute_psnr(pred, target).item())
-        ssim.append(compute_ssim(pred, target).item())
-        if lpips_metric is not None:
-            v = lpips_metric(pred, target)
-            if v is not None:
-                lp.append(v.item())
-        if logger is not None and i < 3:
-            logger.log_images(f"val_{idx}", pred, target, iteration, depth=out["depth"])
-    return ValidationMetrics(iteration=iteration, psnr=float(np.mean(psnr)), ssim=float(np.mean(ssim)),
-                             mse=float(np.mean(mse)), lpips=float(np.mean(lp)) if lp else None,
-                             per_image_psnr=psnr, per_image_ssim=ssim)
+    views = [int(idx) for idx in val_indices[:min(num_images, len(val_indices))]]
+    return evaluate_views(
+        lambda idx: render_image_with_pose(model_coarse, model_fine, val_data.poses[idx], val_data.H, val_data.W,
+                                           val_data.focal, render_config, fxy=fxy),
+        ((f"val_{idx}", idx, val_data.images[idx]) for idx in views), logger, iteration, lpips_metric)
 
 
 def save_checkpoint_with_poses(output_dir, iteration: int, model_coarse, model_fine, camera_params,
@@ -311,32 +289,19 @@ def save_checkpoint_with_poses(output_dir, iteration: int, model_coarse, model_f
     """Reference train_pose_opt.py:548-610: the train.py checkpoint plus ``camera_params``,
     ``optimizer_nerf`` / ``optimizer_poses``, ``initial_poses`` and ``pose_errors``; with
     learned ``intrinsics`` also their state dict as ``intrinsics``."""
-    from .train import checkpoint_config, noise_dict
-    output_dir = Path(output_dir)
-    output_dir.mkdir(parents=True, exist_ok=True)
-    ckpt = {"iteration": iteration, "model_coarse": model_coarse.state_dict(),
-            "camera_params": camera_params.state_dict(), "optimizer_nerf": optimizer_nerf.state_dict(),
-            "initial_poses": camera_params.initial_poses.cpu(), "config": checkpoint_config(config),
-            "mi355x": {"precision": getattr(config.model, "precision", "fp32")}}
+    ckpt = base_checkpoint(iteration, model_coarse, model_fine, config, noise_config, metrics)
+    ckpt.update(camera_params=camera_params.state_dict(), optimizer_nerf=optimizer_nerf.state_dict(),
+                initial_poses=camera_params.initial_poses.cpu())
     window = _window_dict(model_coarse)
     if window is not None:
         ckpt["mi355x"]["pe_window"] = window  # both networks share the schedule
     if intrinsics is not None:
         ckpt["intrinsics"] = intrinsics.state_dict()  # CameraIntrinsics.from_state_dict rebuilds it
-    if model_fine is not None:
-        ckpt["model_fine"] = model_fine.state_dict()
     if optimizer_poses is not None:
         ckpt["optimizer_poses"] = optimizer_poses.state_dict()
-    if metrics is not None:
-        ckpt["metrics"] = metrics
     if pose_errors is not None:
         ckpt["pose_errors"] = pose_errors
-    if noise_config is not None:
-        ckpt["noise_config"] = noise_dict(noise_config)
-    torch.save(ckpt, output_dir / f"checkpoint_{iteration:07d}.pt")
-    torch.save(ckpt, output_dir / "checkpoint_latest.pt")
-    if is_best:
-        torch.save(ckpt, output_dir / "checkpoint_best.pt")
+    write_checkpoint(output_dir, iteration, ckpt, is_best)
 
 
 def generate_experiment_name(scene: str, noise_config: Optional[NoiseConfig], init_mode: str = "noisy") -> str:
@@ -378,14 +343,6 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     the console line only."""
     import torch.distributed as dist
 
-    rank, world = 0, 1
-    if process_group is not None:
-        rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
-    if graph and world > 1 and dist.get_backend(process_group) != "nccl":
-        # the captured step contains the all-reduces: only RCCL collectives are graph-capturable
-        raise ValueError("train_with_pose_optimization(graph=True) with data parallelism needs the nccl (RCCL) "
-                         "backend")
-    check_run_args(config, world, train_data, val_data)
     pe_schedule = None
     if c2f is not None:
         c2f = (float(c2f[0]), float(c2f[1]))
@@ -395,15 +352,9 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
 
         def pe_schedule(iteration, num_freqs):
             return pe_window_weights(c2f_alpha(iteration, n_it, c2f[0], c2f[1], num_freqs), num_freqs)
-    set_seed(config.train.seed)
-    device = config.train.device
-    if device.startswith("cuda") and not torch.cuda.is_available():
-        raise RuntimeError("noisy_src.train_pose_opt needs a ROCm device (no CPU path)")
     exp_name = experiment_name or generate_experiment_name(config.data.scene_name, noise_config, init_mode)
-    output_dir = Path(config.train.output_dir) / exp_name
-    logger = ExperimentLogger(output_dir, exp_name, use_tensorboard=True) if rank == 0 else None
-    if logger is not None:
-        logger.log_config(config)
+    rank, world, device, output_dir, logger, lpips_metric = open_run(
+        config, exp_name, process_group, graph, "train_with_pose_optimization", train_data, val_data)
     if train_data is None:
         root = config.data.data_root if config.data.data_root is not None else Path("data") / "raw"
         train_data = load_blender_data(root, config.data.scene_name, "train", config.data.img_scale, device)
@@ -426,11 +377,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
             raise ValueError(f"focal_init_scale must be positive, got {focal_init_scale}")
         intrinsics = CameraIntrinsics(train_data.focal * focal_init_scale, learn_focal).to(device)
     gt_focal = float(train_data.focal)
-    model_coarse, model_fine = create_nerf_for(config, device)
-    if logger is not None:
-        logger.log_model_info(model_coarse, "model_coarse")
-        if model_fine is not None:
-            logger.log_model_info(model_fine, "model_fine")
+    model_coarse, model_fine = create_nerf_for(config, device, logger)
     _, pixel_sampler = create_pixel_dataset(train_data)
     pixel_sampler.batch_size = config.data.batch_size
     trainer = PoseTrainer(model_coarse, model_fine, camera_params, pixel_sampler, config.render, lr=config.train.lr,
@@ -438,11 +385,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                           translation_reg_weight=translation_reg_weight, process_group=process_group,
                           pe_schedule=pe_schedule, intrinsics=intrinsics, distortion_weight=distortion_weight)
     optimizer_nerf, optimizer_poses = trainer.optimizer_nerf, trainer.optimizer_poses
-    lpips_metric = LPIPSMetric(device=device) if rank == 0 else None
-    if lpips_metric is not None and not lpips_metric.available:
-        lpips_metric = None
     if rank == 0:
-        nc = noise_config
         extra = {}
         if c2f is not None:
             extra["c2f"] = list(c2f)
@@ -451,103 +394,69 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         if intrinsics is not None:
             extra["learn_focal"] = {"mode": learn_focal, "focal_init_scale": focal_init_scale}
         extra["distortion_weight"] = distortion_weight
-        (output_dir / "experiment_config.json").write_text(json.dumps({
-            "scene": config.data.scene_name, "experiment_name": exp_name, "init_mode": init_mode,
+        write_experiment_config(output_dir, config, exp_name, world, noise_config, extra=extra, after_name={
+            "init_mode": init_mode,
             "pose_optimization": {"learn_rotation": learn_rotation, "learn_translation": learn_translation,
                                   "pose_lr": pose_lr, "pose_opt_delay": pose_opt_delay,
                                   "rotation_reg_weight": rotation_reg_weight,
-                                  "translation_reg_weight": translation_reg_weight},
-            "noise_config": {"rotation_noise_deg": nc.rotation_noise_deg, "translation_noise": nc.translation_noise,
-                             "translation_noise_pct": nc.translation_noise_pct, "seed": nc.seed,
-                             "has_noise": nc.has_noise} if nc else None,
-            "num_iterations": config.train.num_iterations, "batch_size": config.data.batch_size,
-            "timestamp": datetime.now().isoformat(), "data_parallel_ranks": world, **extra}, indent=2))
+                                  "translation_reg_weight": translation_reg_weight}})
         log(f"joint NeRF + pose optimisation: {exp_name} -> {output_dir} ({world} rank(s))")
 
-    B = config.data.batch_size
-    rc = config.render
-    val_idx = torch.arange(val_data.images.shape[0], device=device)
-    start = time.time()
-    best_psnr = 0.0
-    lagged = LaggedScalars()  # logged losses read one iteration late: no per-step host sync
-    t_prev = time.time()
-    graphed = None
-
-    def log_iteration(done):
-        if done is None or logger is None:
-            return
-        vals, (it, keys, lr, now, batch_time) = done
-        vm = dict(zip(keys, vals))
-        last = vm.get("loss_fine", vm["loss_coarse"])
-        psnr = -10.0 * math.log10(last) if last > 0 else float("inf")
-        logger.log_training(TrainingMetrics(iteration=it, loss=vm["loss"], loss_coarse=vm["loss_coarse"],
-                                            loss_fine=vm.get("loss_fine"), psnr=psnr, learning_rate=lr,
-                                            time_per_iter=batch_time, rays_per_sec=B / batch_time,
-                                            focal_error_pct=vm.get("focal_error_pct")))
-        if it % config.train.log_every == 0:
-            focal = f" | focal err: {vm['focal_error_pct']:.3f}%" if "focal_error_pct" in vm else ""
-            if "loss_distortion" in vm:
-                focal += f" | distortion: {vm['loss_distortion']:.5f}"
-            log(f"[{it:7d}/{config.train.num_iterations}] loss: {vm['loss']:.5f} | psnr: {psnr:.2f} | "
-                f"lr: {lr:.2e} | poses: {'optimizing' if now else 'frozen'}{focal} | "
-                f"time: {(time.time() - start) / 60:.1f}min")
+    def line(vm, lr, rays_per_sec, optimizing):
+        focal = f" | focal err: {vm['focal_error_pct']:.3f}%" if "focal_error_pct" in vm else ""
+        if "loss_distortion" in vm:
+            focal += f" | distortion: {vm['loss_distortion']:.5f}"
+        return f"lr: {lr:.2e} | poses: {'optimizing' if optimizing else 'frozen'}{focal}"
 
     def learned_fxy():
         return intrinsics.fxy_values() if intrinsics is not None else None
 
+    def checkpoint(iteration, pe, **kw):
+        save_checkpoint_with_poses(output_dir, iteration, model_coarse, model_fine, camera_params, optimizer_nerf,
+                                   optimizer_poses, config, noise_config, pose_errors=pe, intrinsics=intrinsics, **kw)
+
+    B = config.data.batch_size
+    rc = config.render
+    val_idx = torch.arange(val_data.images.shape[0], device=device)
+    best_psnr = 0.0
+    graphed = None
+    ilog = IterationLog(logger, config, process_group, line, log)
     for iteration in range(config.train.num_iterations):
         # the global batch, identical on every rank (one process in graph mode: the gather
         # kernel writes it straight into the graphs' static inputs).  The draws stay in the
         # eager order: randint, rand, rand
         batch = pixel_sampler.sample_batch(out=graphed.static if (graphed is not None and world == 1) else None)
         now = iteration >= pose_opt_delay
-        t_rand = torch.rand(B, rc.num_samples, device=device) if rc.perturb else None
-        u = torch.rand(B, rc.num_samples_fine, device=device) if (rc.use_hierarchical and model_fine) else None
-        sl = rank_slice(B, rank, world) if world > 1 else slice(0, B)
-        args = (batch.slice(sl) if world > 1 else batch, now, None if t_rand is None else t_rand[sl],
-                None if u is None else u[sl])
+        sl, (t_rand, u) = slice_for_rank(B, rank, world, *draw_randoms(B, rc, model_fine is not None, device))
+        args = (batch.slice(sl) if world > 1 else batch, now, t_rand, u)
         if graph and iteration >= 1:
             if graphed is None:  # after one eager step: the networks' Adam state exists
                 graphed = GraphedPoseTrainer(trainer, args[0], args[2], args[3], warmup=0)
             m = graphed.step(*args, iteration=iteration)  # eager once more where the pose Adam's state is new
         else:
             m = trainer.step(*args, iteration=iteration)
-        keys = ["loss", "loss_coarse"] + [k for k in ("loss_fine", "loss_distortion") if k in m]
-        vals = [m[k] for k in keys]
-        if intrinsics is not None:  # a device scalar like the losses: read one iteration late
-            keys.append("focal_error_pct")
-            vals.append(intrinsics.focal_error_pct(gt_focal))
-        t_now = time.time()
-        log_iteration(lagged.push(mean_over_ranks(vals, process_group),
-                                  (iteration, keys, optimizer_nerf.param_groups[0]["lr"], now, t_now - t_prev)))
-        t_prev = t_now
-        if logger is None:
-            continue
-        if iteration > 0 and (iteration % config.train.val_every == 0 or iteration % config.train.save_every == 0):
-            log_iteration(lagged.flush())
-        if iteration % config.train.val_every == 0 and iteration > 0:
+        # the focal error is a device scalar like the losses: read one iteration late
+        ilog.push(iteration, m, optimizer_nerf.param_groups[0]["lr"],
+                  {"focal_error_pct": intrinsics.focal_error_pct(gt_focal)} if intrinsics is not None else None, now)
+        what = due(iteration, config.train.val_every, config.train.save_every) if logger is not None else None
+        if what:
+            ilog.flush()
             pe = camera_params.compute_pose_errors(gt_train_poses)
-            vmx = evaluate_with_poses(model_coarse, model_fine, camera_params, val_data, val_idx, rc, logger,
-                                      iteration, num_images=5, lpips_metric=lpips_metric, fxy=learned_fxy())
-            logger.log_validation(vmx)
-            is_best = vmx.psnr > best_psnr
-            best_psnr = max(best_psnr, vmx.psnr)
-            focal = (f"; focal error {float(intrinsics.focal_error_pct(gt_focal)):.3f} %"
-                     if intrinsics is not None else "")
-            log(f"  validation @ {iteration}: PSNR {vmx.psnr:.2f} dB; pose error rot "
-                f"{pe['rotation_error_mean']:.3f} deg, trans {pe['translation_error_mean']:.4f}{focal}")
-            save_checkpoint_with_poses(output_dir, iteration, model_coarse, model_fine, camera_params,
-                                       optimizer_nerf, optimizer_poses, config, noise_config,
-                                       metrics={"psnr": vmx.psnr, "ssim": vmx.ssim}, pose_errors=pe,
-                                       is_best=is_best, intrinsics=intrinsics)
-            t_prev = time.time()  # the next iteration's time excludes the validation
-        elif iteration % config.train.save_every == 0 and iteration > 0:
-            pe = camera_params.compute_pose_errors(gt_train_poses)
-            save_checkpoint_with_poses(output_dir, iteration, model_coarse, model_fine, camera_params,
-                                       optimizer_nerf, optimizer_poses, config, noise_config, pose_errors=pe,
-                                       intrinsics=intrinsics)
-            t_prev = time.time()
-    log_iteration(lagged.flush())
+            if what == "val":
+                vmx = evaluate_with_poses(model_coarse, model_fine, camera_params, val_data, val_idx, rc, logger,
+                                          iteration, num_images=5, lpips_metric=lpips_metric, fxy=learned_fxy())
+                logger.log_validation(vmx)
+                is_best = vmx.psnr > best_psnr
+                best_psnr = max(best_psnr, vmx.psnr)
+                focal = (f"; focal error {float(intrinsics.focal_error_pct(gt_focal)):.3f} %"
+                         if intrinsics is not None else "")
+                log(f"  validation @ {iteration}: PSNR {vmx.psnr:.2f} dB; pose error rot "
+                    f"{pe['rotation_error_mean']:.3f} deg, trans {pe['translation_error_mean']:.4f}{focal}")
+                checkpoint(iteration, pe, metrics={"psnr": vmx.psnr, "ssim": vmx.ssim}, is_best=is_best)
+            else:
+                checkpoint(iteration, pe)
+            ilog.pause()
+    ilog.flush()
     if pe_schedule is not None:
         # the final evaluation and checkpoint: the window at the end of the schedule
         trainer.set_pe_windows(config.train.num_iterations)
@@ -562,10 +471,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                     config.train.num_iterations, num_images=val_data.images.shape[0],
                                     lpips_metric=lpips_metric, fxy=learned_fxy())
         # (the reference does not write the final evaluation to val_metrics.csv, :1002-1019)
-        save_checkpoint_with_poses(output_dir, config.train.num_iterations, model_coarse, model_fine, camera_params,
-                                   optimizer_nerf, optimizer_poses, config, noise_config,
-                                   metrics={"psnr": final.psnr, "ssim": final.ssim}, pose_errors=final_pe,
-                                   intrinsics=intrinsics)
+        checkpoint(config.train.num_iterations, final_pe, metrics={"psnr": final.psnr, "ssim": final.ssim})
         with torch.no_grad():
             final_poses = camera_params.get_all_poses()
         record = {"initial_poses": camera_params.initial_poses.cpu(), "optimized_poses": final_poses.cpu(),
@@ -586,16 +492,6 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     return result
 
 
-def create_nerf_for(config: NeRFConfig, device):
-    """create_nerf + .to(device); no fine network without hierarchical sampling
-    (train_pose_opt.py:772-777)."""
-    from .model import create_nerf
-    mc, mf = create_nerf(config.model)
-    mc = mc.to(device)
-    mf = mf.to(device) if config.render.use_hierarchical else None
-    return mc, mf
-
-
 # what the measured table shows (DESIGN.md section 4b, profiles/pose_graph_ab.json)
 GRAPH_HELP = ("replay the joint step from hipGraphs, one for frozen poses and one for optimising (same results as "
               "eager; with RCCL data parallelism the all-reduces are captured too). Measured on one MI355X, bf16 "
@@ -609,12 +505,8 @@ def build_arg_parser():
     ``--distortion_weight``."""
     import argparse
     ap = argparse.ArgumentParser(description="Joint NeRF + camera pose optimisation (MI355X HIP path)")
-    ap.add_argument("--scene", type=str, default="lego")
-    ap.add_argument("--data_root", type=str, default=None)
-    ap.add_argument("--img_scale", type=float, default=0.5)
-    ap.add_argument("--batch_size", type=int, default=1024, help="global batch (pixels) over all ranks")
-    ap.add_argument("--num_iters", type=int, default=50000)
-    ap.add_argument("--lr", type=float, default=5e-4)
+    add_common_args(ap, "scene data_root img_scale batch_size num_iters lr", num_iters=dict(default=50000),
+                    batch_size=dict(help="global batch (pixels) over all ranks"))
     ap.add_argument("--init_mode", type=str, default="noisy", choices=["noisy", "clean"])
     ap.add_argument("--pose_lr", type=float, default=1e-4)
     ap.add_argument("--pose_opt_delay", type=int, default=1000)
@@ -622,21 +514,9 @@ def build_arg_parser():
     ap.add_argument("--no_learn_translation", action="store_true")
     ap.add_argument("--rotation_reg_weight", type=float, default=0.01)
     ap.add_argument("--translation_reg_weight", type=float, default=0.001)
-    ap.add_argument("--rotation_noise", type=float, default=0.0)
-    ap.add_argument("--translation_noise", type=float, default=0.0)
-    ap.add_argument("--translation_noise_pct", type=float, default=0.0)
-    ap.add_argument("--noise_seed", type=int, default=None)
-    ap.add_argument("--no_hierarchical", action="store_true")
-    ap.add_argument("--num_samples", type=int, default=64)
-    ap.add_argument("--num_samples_fine", type=int, default=128)
-    ap.add_argument("--log_every", type=int, default=100)
-    ap.add_argument("--val_every", type=int, default=2500)
-    ap.add_argument("--save_every", type=int, default=10000)
-    ap.add_argument("--output_dir", type=str, default="outputs")
-    ap.add_argument("--device", type=str, default="cuda")
-    ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
-                    help="MLP operand precision (fp32 = the reference's numerics)")
+    add_common_args(ap, "rotation_noise translation_noise translation_noise_pct noise_seed no_hierarchical num_samples "
+                        "num_samples_fine log_every val_every save_every output_dir device seed precision",
+                    val_every=dict(default=2500))
     ap.add_argument("--graph", action="store_true", help=GRAPH_HELP)
     ap.add_argument("--c2f", type=float, nargs=2, default=None, metavar=("START", "END"),
                     help="coarse-to-fine positional encoding (BARF): the frequencies of both encoders are "
@@ -650,43 +530,23 @@ def build_arg_parser():
     ap.add_argument("--focal_init_scale", type=float, default=1.0,
                     help="with --learn_focal: start from this multiple of the dataset's focal length (the "
                          "deterministic counterpart of the pose-noise flags)")
-    ap.add_argument("--distortion_weight", type=float, default=0.0,
-                    help="weight of the distortion regulariser on the rendering network's ray weights "
-                         "(mip-NeRF 360; 0 = off, 0.01 is the paper's)")
+    add_common_args(ap, "distortion_weight")
     return ap
 
 
 def main(argv=None) -> None:
     """``python -m noisy_src.train_pose_opt`` (or under ``torchrun`` for data parallelism)."""
-    from .config import DataConfig, ModelConfig, TrainConfig
-
     a = build_arg_parser().parse_args(argv)
-    noise_config = None
-    if a.rotation_noise > 0 or a.translation_noise > 0 or a.translation_noise_pct > 0:
-        noise_config = NoiseConfig(rotation_noise_deg=a.rotation_noise, translation_noise=a.translation_noise,
-                                   translation_noise_pct=a.translation_noise_pct, seed=a.noise_seed)
-    pg, rank, world, device = init_distributed(a.device)
-    cfg = NeRFConfig(
-        model=ModelConfig(precision=a.precision),
-        render=RenderConfig(use_hierarchical=not a.no_hierarchical, num_samples=a.num_samples,
-                            num_samples_fine=a.num_samples_fine),
-        data=DataConfig(scene_name=a.scene, data_root=Path(a.data_root) if a.data_root else None,
-                        img_scale=a.img_scale, batch_size=a.batch_size),
-        train=TrainConfig(lr=a.lr, num_iterations=a.num_iters, output_dir=Path(a.output_dir), device=device,
-                          seed=a.seed, log_every=a.log_every, val_every=a.val_every, save_every=a.save_every))
-    name = [generate_experiment_name(a.scene, noise_config, a.init_mode)]
-    if pg is not None:
-        import torch.distributed as dist
-        dist.broadcast_object_list(name, src=0, group=pg)
-    train_with_pose_optimization(cfg, noise_config, a.init_mode, a.pose_lr, a.pose_opt_delay,
-                                 not a.no_learn_rotation, not a.no_learn_translation, a.rotation_reg_weight,
-                                 a.translation_reg_weight, process_group=pg, experiment_name=name[0],
-                                 graph=a.graph, c2f=tuple(a.c2f) if a.c2f is not None else None,
-                                 fixed_small_angle=a.fixed_small_angle, learn_focal=a.learn_focal,
-                                 focal_init_scale=a.focal_init_scale, distortion_weight=a.distortion_weight)
-    if pg is not None:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+
+    def call(cfg, noise_config, pg, name):
+        train_with_pose_optimization(cfg, noise_config, a.init_mode, a.pose_lr, a.pose_opt_delay,
+                                     not a.no_learn_rotation, not a.no_learn_translation, a.rotation_reg_weight,
+                                     a.translation_reg_weight, process_group=pg, experiment_name=name,
+                                     graph=a.graph, c2f=tuple(a.c2f) if a.c2f is not None else None,
+                                     fixed_small_angle=a.fixed_small_angle, learn_focal=a.learn_focal,
+                                     focal_init_scale=a.focal_init_scale, distortion_weight=a.distortion_weight)
+
+    run_cli(a, lambda noise_config, world: generate_experiment_name(a.scene, noise_config, a.init_mode), call)
 
 
 __all__ = ["set_seed", "CameraPoseParameters", "CameraIntrinsics", "train_step_with_poses", "render_image_with_pose",
