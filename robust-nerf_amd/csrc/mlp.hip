@@ -55,11 +55,12 @@ bool add_stream_layer(StreamDesc& sd, int nchunks, int chunk_kb, int load_kb = -
     return true;
 }
 
-// 16-bit forward arguments; the saved region's offsets are the caller's (training: make_sizes)
-RbmArgs rbm_args(const MlpPlan& p, const void* packed, const float* params, const float* x, const float* d, int64_t M,
-                 int64_t tiles, float* rgb, float* sigma, void* saved) {
-    RbmArgs r;
-    std::memset(&r, 0, sizeof(r));
+// The forward chains' shared fields (FwdIO's, in RbmArgs or FwdArgs), assigned here and
+// nowhere else.  sv_off: the saved tensors' offsets of the training layout (make_sizes), or
+// null where none is stored (the frozen field's masks-only forward, whose mask_off is 0)
+template <class A>
+void fwd_io(A& r, const MlpPlan& p, const void* packed, const float* params, const float* x, const float* d,
+            int64_t M, int64_t tiles, float* rgb, float* sigma, void* saved, const int64_t* sv_off, int64_t mask_off) {
     r.packed = static_cast<const char*>(packed);
     r.params = params;
     r.x = x;
@@ -73,24 +74,23 @@ RbmArgs rbm_args(const MlpPlan& p, const void* packed, const float* params, cons
     r.Ld = p.Ld;
     r.n_layers = p.n_layers;
     r.skips = p.skips;
-    r.base = p.lin[0].pk_fwd;
-    r.vhead = p.vhead;
     r.sig_b = p.sig_b;
     r.rgb_b = p.rgb_b;
+    for (int t = 0; t < p.n_saved; ++t) r.sv_off[t] = sv_off ? sv_off[t] : 0;
     r.sv_feat = p.sv_feat;
     r.sv_denc = p.sv_denc;
     r.sv_hc = p.sv_hc;
+    r.mask_off = mask_off;
     r.n_mask = p.n_mask;
-    return r;
 }
 
-// 16-bit dX chain arguments; the workspace offsets, lists and scratch tiles are the caller's
-BwdrArgs bwdr_args(const MlpPlan& p, const void* packed, int64_t M, int64_t tiles, int64_t nseg, const float* rgb,
-                   const float* sigma, const void* saved, const float* g_rgb, const float* g_sigma, char* wsb,
-                   const uint8_t* tflags, const uint32_t* blkcnt) {
-    const int n = p.n_layers;
-    BwdrArgs r;
-    std::memset(&r, 0, sizeof(r));
+// The dX chains' shared fields (DxIO's, in BwdrArgs or BwdArgs), assigned here and nowhere
+// else.  ws_off: the dz images' offsets by workspace tensor id (p.n_ws of them); dw_list /
+// count: null for the input-only chain, which builds no dW list
+template <class A>
+void dx_io(A& r, const MlpPlan& p, const void* packed, int64_t M, int64_t tiles, int64_t nseg, const float* rgb,
+           const float* sigma, const void* saved, int64_t mask_off, const float* g_rgb, const float* g_sigma, char* wsb,
+           const int64_t* ws_off, const uint8_t* tflags, const uint32_t* blkcnt, uint32_t* dw_list, uint32_t* count) {
     r.gscale = grad_scale(p.prec);
     r.packed = static_cast<const char*>(packed);
     r.rgb = rgb;
@@ -104,15 +104,16 @@ BwdrArgs bwdr_args(const MlpPlan& p, const void* packed, int64_t M, int64_t tile
     r.flags = tflags;
     r.blk_count = blkcnt;
     r.nseg = nseg;
-    r.n_layers = n;
-    r.base = p.lin[n + 1].pk_bwdr;
+    r.dw_list = dw_list;
+    r.count = count;
+    r.n_layers = p.n_layers;
     r.vrgb = p.vrgb;
-    r.vhead = p.vhead;
+    r.mask_off = mask_off;
     r.n_mask = p.n_mask;
+    for (int t = 0; t < p.n_ws; ++t) r.ws_off[t] = ws_off[t];
     r.ws_feat = p.ws_feat;
     r.ws_dir = p.ws_dir;
     r.ws_heads = p.ws_heads;
-    return r;
 }
 
 }  // namespace
@@ -235,44 +236,23 @@ int nr_mlp_forward(const NrMlpConfig* cfg, const void* packed, const float* para
     const MlpSizes z = make_sizes(p, M);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.prec != NR_PREC_FP32) {
-        RbmArgs r = rbm_args(p, packed, params, x, d, M, z.tiles, rgb, sigma, saved);
-        for (int t = 0; t < p.n_saved; ++t) r.sv_off[t] = z.saved_off[t];
-        r.mask_off = z.mask_off;
-        return launch_fwd_rbm(p, r, saved != nullptr, s);
+        RbmArgs r{};
+        fwd_io(r, p, packed, params, x, d, M, z.tiles, rgb, sigma, saved, z.saved_off, z.mask_off);
+        r.base = p.lin[0].pk_fwd;
+        r.vhead = p.vhead;
+        return launch_fwd_rbm(p, r, saved ? FwdSave::Train : FwdSave::Infer, s);
     }
-    FwdArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.packed = static_cast<const char*>(packed);
-    a.params = params;
-    a.x = x;
-    a.d = d;
-    a.rgb = rgb;
-    a.sigma = sigma;
-    a.saved = static_cast<char*>(saved);
-    a.M = M;
-    a.tiles = z.tiles;
-    a.L = p.L;
-    a.Ld = p.Ld;
-    a.n_layers = p.n_layers;
-    a.skips = p.skips;
+    FwdArgs a{};
+    fwd_io(a, p, packed, params, x, d, M, z.tiles, rgb, sigma, saved, z.saved_off, z.mask_off);
     a.sd.base = p.lin[0].pk_fwd;
     for (int l = 0; l < p.n_lin; ++l) {
         const LinearDesc& dl = p.lin[l];
         NR_REQUIRE(add_stream_layer(a.sd, dl.KB, dl.NB * p.fpb),
                    "nr_mlp_forward: the weight stream exceeds kMaxChunks = %d chunks", kMaxChunks);
         a.vb[l] = dl.vb;
-        a.bo[l] = dl.b_off;
     }
     a.vsig = p.vsig;
     a.vrgb = p.vrgb;
-    a.sig_b = p.sig_b;
-    a.rgb_b = p.rgb_b;
-    for (int t = 0; t < p.n_saved; ++t) a.sv_off[t] = z.saved_off[t];
-    a.sv_feat = p.sv_feat;
-    a.sv_denc = p.sv_denc;
-    a.sv_hc = p.sv_hc;
-    a.mask_off = z.mask_off;
-    a.n_mask = p.n_mask;
     return launch_fwd(p, a, saved != nullptr, s);
 }
 
@@ -303,45 +283,29 @@ int nr_mlp_backward_dx(const NrMlpConfig* cfg, const void* packed, const float* 
     if (p.prec != NR_PREC_FP32) {
         // 16-bit: the row-block-major dX chain (mlp_bwd_rbm.inc); g_x / g_d come from a
         // separate pass over the dz images it stores (mlp_dinput_kernel)
-        BwdrArgs r = bwdr_args(p, packed, M, z.tiles, z.nseg, rgb, sigma, saved, g_rgb, g_sigma, wsb, tflags, blkcnt);
-        r.dw_list = dwlist;
-        r.count = tcount;
+        BwdrArgs r{};
+        dx_io(r, p, packed, M, z.tiles, z.nseg, rgb, sigma, saved, z.mask_off, g_rgb, g_sigma, wsb, z.ws_off, tflags,
+              blkcnt, dwlist, tcount);
+        r.base = p.lin[n + 1].pk_bwdr;
+        r.vhead = p.vhead;
         r.scratch_base = z.tiles_alloc - kScratchTiles;
-        r.mask_off = z.mask_off;
-        for (int t = 0; t < p.n_ws; ++t) r.ws_off[t] = z.ws_off[t];
-        const int rc = launch_bwd_rbm(p, r, s);
+        const int rc = launch_bwd_rbm(p, r, false, s);
         if (rc != NR_OK || !(g_x || g_d)) return rc;
-        return input_grads16(p, z, r.packed, x, d, g_x, g_d, wsb, M, s);
+        return input_grads16(p, din_offsets(p, z), r.packed, x, d, g_x, g_d, wsb, M, s);
     }
     // fp32: the chunk-major chain, which computes g_x / g_d itself when they are wanted
     const bool wx = g_x != nullptr || g_d != nullptr;
-    BwdArgs b;
-    std::memset(&b, 0, sizeof(b));
-    b.packed = static_cast<const char*>(packed);
-    b.gscale = grad_scale(p.prec);
-    b.inv_gscale = 1.0f / b.gscale;
-    b.params = params;
+    BwdArgs b{};
+    dx_io(b, p, packed, M, z.tiles, z.nseg, rgb, sigma, saved, z.mask_off, g_rgb, g_sigma, wsb, z.ws_off, tflags, blkcnt,
+          dwlist, tcount);
     b.x = x;
     b.d = d;
-    b.rgb = rgb;
-    b.sigma = sigma;
-    b.g_rgb = g_rgb;
-    b.g_sigma = g_sigma;
-    b.g_x = g_x;
-    b.g_d = g_d;
-    b.saved = static_cast<const char*>(saved);
-    b.ws = wsb;
-    b.M = M;
-    b.tiles = z.tiles;
-    b.flags = tflags;
-    b.blk_count = blkcnt;
-    b.nseg = z.nseg;
-    b.dw_list = dwlist;
-    b.count = tcount;
     b.L = p.L;
     b.Ld = p.Ld;
-    b.n_layers = n;
     b.skips = p.skips;
+    b.g_x = g_x;
+    b.g_d = g_d;
+    b.inv_gscale = 1.0f / b.gscale;
     // a skip layer's W^T chunk is [h rows | x_enc rows] and dir's is [feat rows |
     // d_enc rows]: without g_x / g_d only the first 8 row blocks are loaded
     bool stream_fits = true;
@@ -356,13 +320,6 @@ int nr_mlp_backward_dx(const NrMlpConfig* cfg, const void* packed, const float* 
     if (wx) add_T(0);
     NR_REQUIRE(stream_fits, "nr_mlp_backward_dx: the weight stream exceeds kMaxChunks = %d chunks", kMaxChunks);
     b.vsig = p.vsig;
-    b.vrgb = p.vrgb;
-    b.mask_off = z.mask_off;
-    b.n_mask = p.n_mask;
-    for (int t = 0; t < p.n_ws; ++t) b.ws_off[t] = z.ws_off[t];
-    b.ws_feat = p.ws_feat;
-    b.ws_dir = p.ws_dir;
-    b.ws_heads = p.ws_heads;
     if (!p.dense_bwd) {
         // the chain writes g_x / g_d of the active tiles only: the rest are exactly zero
         for (float* g : {g_x, g_d})
@@ -521,8 +478,11 @@ int nr_mlp_forward_frozen(const NrMlpConfig* cfg, const void* packed, const floa
     // fp32: the training forward (its backward reads the activations)
     if (p.prec == NR_PREC_FP32) return nr_mlp_forward(cfg, packed, params, x, d, M, rgb, sigma, saved_frozen, stream);
     const FrozenSizes f = make_frozen_sizes(p, M);
-    const RbmArgs r = rbm_args(p, packed, params, x, d, M, f.tiles, rgb, sigma, saved_frozen);  // mask_off = 0
-    return launch_fwd_rbm_masks(p, r, static_cast<hipStream_t>(stream));
+    RbmArgs r{};
+    fwd_io(r, p, packed, params, x, d, M, f.tiles, rgb, sigma, saved_frozen, nullptr, 0);
+    r.base = p.lin[0].pk_fwd;
+    r.vhead = p.vhead;
+    return launch_fwd_rbm(p, r, FwdSave::Masks, static_cast<hipStream_t>(stream));
 }
 
 int nr_mlp_backward_input(const NrMlpConfig* cfg, const void* packed, const float* params, const float* x,
@@ -548,18 +508,19 @@ int nr_mlp_backward_input(const NrMlpConfig* cfg, const void* packed, const floa
     uint8_t* tflags = reinterpret_cast<uint8_t*>(wsb + f.flags_off);
     uint32_t* blkcnt = reinterpret_cast<uint32_t*>(wsb + f.blkcnt_off);
     if (const int rc = launch_tile_flags(g_rgb, g_sigma, M, p.dense_bwd, f.nseg, tflags, blkcnt, s)) return rc;
-    BwdrArgs r = bwdr_args(p, packed, M, f.tiles, f.nseg, rgb, sigma, saved_frozen, g_rgb, g_sigma, wsb, tflags, blkcnt);
-    r.scratch_base = f.scratch_base;  // mask_off = 0; no dW list
+    // the dz images the input-only chain stores, by workspace tensor id; no dW list
+    int64_t ws_off[kMaxTrunk + 3] = {};
+    for (int l = 0; l < p.n_layers; ++l) ws_off[WS_DZ0 + l] = f.dz_off[l];
+    ws_off[p.ws_dir] = f.dz_dir_off;
+    BwdrArgs r{};
+    dx_io(r, p, packed, M, f.tiles, f.nseg, rgb, sigma, saved_frozen, 0, g_rgb, g_sigma, wsb, ws_off, tflags, blkcnt,
+          nullptr, nullptr);
+    r.base = p.lin[p.n_layers + 1].pk_bwdr;
+    r.vhead = p.vhead;
+    r.scratch_base = f.scratch_base;
     r.keep_dz = f.keep_dz;
-    // the offsets mlp_dinput_kernel reads, in the training structs' terms
-    MlpSizes z;
-    std::memset(&z, 0, sizeof(z));
-    z.tiles = f.tiles;
-    z.flags_off = f.flags_off;
-    for (int l = 0; l < p.n_layers; ++l) z.ws_off[WS_DZ0 + l] = r.ws_off[WS_DZ0 + l] = f.dz_off[l];
-    z.ws_off[p.ws_dir] = r.ws_off[p.ws_dir] = f.dz_dir_off;
-    if (const int rc = launch_bwd_rbm_input(p, r, s)) return rc;
-    return input_grads16(p, z, r.packed, x, d, g_x, g_d, wsb, M, s);
+    if (const int rc = launch_bwd_rbm(p, r, true, s)) return rc;
+    return input_grads16(p, din_offsets(p, f), r.packed, x, d, g_x, g_d, wsb, M, s);
 }
 
 int64_t nr_mlp_active_tiles_offset(const NrMlpConfig* cfg, int64_t M) {

@@ -2,7 +2,6 @@
 // (mlp_fwd_rbm.inc), backward dX chain (mlp_bwd_rbm.inc) and the input gradients
 // g_x / g_d as a pass over the stored dz images (mlp_dinput_kernel).
 #include <algorithm>
-#include <cstring>
 
 #include "mlp_dev.hpp"
 #include "mlp_launch.hpp"
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(kDinNT) void mlp_dinput_kernel(DinArgs a) {
             for (int s = 0; s < a.nsrc; ++s) {
                 InBlk<PREC> b[kHB];
 #pragma unroll
-                for (int ob = 0; ob < kHB; ++ob) load_img<PREC>(a.ws + a.dz_off[s], tile_u, kHB, ob, b[ob], lane);
+                for (int ob = 0; ob < kHB; ++ob) load_img<PREC>(a.ws + a.dz_off[s], tile_u, kHB, ob, b[ob]);
 #pragma unroll
                 for (int ob = 0; ob < kHB; ++ob)
 #pragma unroll
@@ -125,14 +124,7 @@ __global__ __launch_bounds__(kDinNT) void mlp_dinput_kernel(DinArgs a) {
                 for (int r = 0; r < 16; ++r)
                     pe_fast_bwd(pr, 32 * kb + acc_row(r, 0), 32 * kb + acc_row(r, 1), h != 0, a.L, dxe[kb][r], g0, g1,
                                 g2);
-            g0 += __shfl_xor(g0, 32);
-            g1 += __shfl_xor(g1, 32);
-            g2 += __shfl_xor(g2, 32);
-            if (valid && h == 0) {
-                a.g_x[3 * m] = g0 * a.inv_gscale;
-                a.g_x[3 * m + 1] = g1 * a.inv_gscale;
-                a.g_x[3 * m + 2] = g2 * a.inv_gscale;
-            }
+            store_input_grad(a.g_x, m, valid && h == 0, a.inv_gscale, g0, g1, g2);
         }
         if constexpr (DB > 0) {
             if (a.g_d) {
@@ -142,7 +134,7 @@ __global__ __launch_bounds__(kDinNT) void mlp_dinput_kernel(DinArgs a) {
                 const int f0 = 2 * a.nsrc * kHB * XB;
                 for (int ob = 0; ob < a.nc; ++ob) {
                     InBlk<PREC> b;
-                    load_img<PREC>(a.ws + a.dz_dir_off, tile_u, a.nc, ob, b, lane);
+                    load_img<PREC>(a.ws + a.dz_dir_off, tile_u, a.nc, ob, b);
 #pragma unroll
                     for (int q = 0; q < DB; ++q) {
                         const int f = f0 + (ob * DB + q) * 2;
@@ -159,14 +151,7 @@ __global__ __launch_bounds__(kDinNT) void mlp_dinput_kernel(DinArgs a) {
                     for (int r = 0; r < 16; ++r)
                         pe_fast_bwd(pr, 32 * kb + acc_row(r, 0), 32 * kb + acc_row(r, 1), h != 0, a.Ld, dd[kb][r], g0,
                                     g1, g2);
-                g0 += __shfl_xor(g0, 32);
-                g1 += __shfl_xor(g1, 32);
-                g2 += __shfl_xor(g2, 32);
-                if (valid && h == 0) {
-                    a.g_d[3 * m] = g0 * a.inv_gscale;
-                    a.g_d[3 * m + 1] = g1 * a.inv_gscale;
-                    a.g_d[3 * m + 2] = g2 * a.inv_gscale;
-                }
+                store_input_grad(a.g_d, m, valid && h == 0, a.inv_gscale, g0, g1, g2);
             }
         }
     }
@@ -174,7 +159,29 @@ __global__ __launch_bounds__(kDinNT) void mlp_dinput_kernel(DinArgs a) {
 
 namespace {
 
-template <int PREC, bool TRAIN, bool ACT = TRAIN>
+template <int PREC>
+int launch_dinput(const MlpPlan& p, const DinArgs& a, hipStream_t s) {
+    const size_t lds = static_cast<size_t>(din_frags(a.nsrc, p.XB, p.DB, a.nc)) * kFragBytes;
+    const bool alds = lds <= 160 * 1024;
+    // enough workgroups for 2 per CU (the staging is amortised over ~6 tiles per wave)
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(ceil_div_ll(a.tiles, kDinNT / 64), 512))),
+        block(kDinNT);
+    const bool found = dispatch_model(p, [&](auto xb, auto db) {
+        constexpr int XB = decltype(xb)::value, DB = decltype(db)::value;
+        if (alds)
+            hipLaunchKernelGGL((mlp_dinput_kernel<PREC, XB, DB, true>), grid, block, lds, s, a);
+        else
+            hipLaunchKernelGGL((mlp_dinput_kernel<PREC, XB, DB, false>), grid, block, 0, s, a);
+    });
+    if (!found) {
+        set_error("nr_mlp_backward_dx: no input-gradient kernel for XB=%d DB=%d", p.XB, p.DB);
+        return NR_EARG;
+    }
+    return check_launch("nr_mlp_backward_dx (input gradients)");
+}
+
+// TRAIN: the ReLU masks are stored; ACT: the activations too
+template <int PREC, bool TRAIN, bool ACT>
 int launch_fwd_rbm_t(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
     // every chunk fits a slot (checked at compile time per layer shape).  Eight waves per
     // workgroup at every size: four- and six-wave workgroups for small launches (all CUs
@@ -184,23 +191,18 @@ int launch_fwd_rbm_t(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
     constexpr int W = kRbmWaves;
     const dim3 grid(static_cast<unsigned>(ceil_div_ll(a.tiles, W))), block(W * 64);
     const size_t lds = rbm_lds_bytes(p.XB, W);
-#define NR_FWDR(XB_, DB_)                                                                           \
-    if (p.XB == XB_ && p.DB == DB_) {                                                               \
-        hipLaunchKernelGGL((mlp_fwd_rbm_kernel<PREC, XB_, DB_, TRAIN, W, ACT>), grid, block, lds, s, a); \
-        return check_launch("nr_mlp_forward");                                                      \
+    const bool found = dispatch_model(p, [&](auto xb, auto db) {
+        hipLaunchKernelGGL((mlp_fwd_rbm_kernel<PREC, decltype(xb)::value, decltype(db)::value, TRAIN, W, ACT>), grid,
+                           block, lds, s, a);
+    });
+    if (!found) {
+        set_error("nr_mlp_forward: no kernel instance for XB=%d DB=%d", p.XB, p.DB);
+        return NR_EARG;
     }
-    NR_FWDR(2, 1)
-#ifndef NR_MLP_DEV
-    NR_FWDR(2, 0)
-    NR_FWDR(1, 1)
-    NR_FWDR(1, 0)
-#endif
-#undef NR_FWDR
-    set_error("nr_mlp_forward: no kernel instance for XB=%d DB=%d", p.XB, p.DB);
-    return NR_EARG;
+    return check_launch("nr_mlp_forward");
 }
 
-template <int PREC, bool INPUT = false>
+template <int PREC, bool INPUT>
 int launch_bwd_rbm_t(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
     constexpr int W = kRbmWaves;
     // the masks of every layer in LDS where they fit (up to 10 trunk layers), else read in place
@@ -215,70 +217,41 @@ int launch_bwd_rbm_t(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
     return check_launch(INPUT ? "nr_mlp_backward_input" : "nr_mlp_backward_dx");
 }
 
-template <int PREC>
-int launch_dinput(const MlpPlan& p, const DinArgs& a, hipStream_t s) {
-    const size_t lds = static_cast<size_t>(din_frags(a.nsrc, p.XB, p.DB, a.nc)) * kFragBytes;
-    const bool alds = lds <= 160 * 1024;
-    // enough workgroups for 2 per CU (the staging is amortised over ~6 tiles per wave)
-    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(ceil_div_ll(a.tiles, kDinNT / 64), 512))),
-        block(kDinNT);
-#define NR_DIN(XB_, DB_)                                                                                  \
-    if (p.XB == XB_ && p.DB == DB_) {                                                                     \
-        if (alds)                                                                                         \
-            hipLaunchKernelGGL((mlp_dinput_kernel<PREC, XB_, DB_, true>), grid, block, lds, s, a);        \
-        else                                                                                              \
-            hipLaunchKernelGGL((mlp_dinput_kernel<PREC, XB_, DB_, false>), grid, block, 0, s, a);         \
-        return check_launch("nr_mlp_backward_dx (input gradients)");                                     \
-    }
-    NR_DIN(2, 1)
-#ifndef NR_MLP_DEV
-    NR_DIN(2, 0)
-    NR_DIN(1, 1)
-    NR_DIN(1, 0)
-#endif
-#undef NR_DIN
-    set_error("nr_mlp_backward_dx: no input-gradient kernel for XB=%d DB=%d", p.XB, p.DB);
-    return NR_EARG;
-}
-
 }  // namespace
 
-int launch_fwd_rbm(const MlpPlan& p, const RbmArgs& a, bool train, hipStream_t s) {
-    if (p.prec == NR_PREC_BF16)
-        return train ? launch_fwd_rbm_t<NR_PREC_BF16, true>(p, a, s) : launch_fwd_rbm_t<NR_PREC_BF16, false>(p, a, s);
-    return train ? launch_fwd_rbm_t<NR_PREC_FP16, true>(p, a, s) : launch_fwd_rbm_t<NR_PREC_FP16, false>(p, a, s);
+int launch_fwd_rbm(const MlpPlan& p, const RbmArgs& a, FwdSave save, hipStream_t s) {
+    return dispatch_prec16(p.prec, [&](auto prec) {
+        constexpr int PREC = decltype(prec)::value;
+        switch (save) {
+            case FwdSave::Train: return launch_fwd_rbm_t<PREC, true, true>(p, a, s);
+            case FwdSave::Masks: return launch_fwd_rbm_t<PREC, true, false>(p, a, s);
+            default: return launch_fwd_rbm_t<PREC, false, false>(p, a, s);
+        }
+    });
 }
 
-int launch_bwd_rbm(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
-    return p.prec == NR_PREC_BF16 ? launch_bwd_rbm_t<NR_PREC_BF16>(p, a, s) : launch_bwd_rbm_t<NR_PREC_FP16>(p, a, s);
-}
-
-int launch_fwd_rbm_masks(const MlpPlan& p, const RbmArgs& a, hipStream_t s) {
-    return p.prec == NR_PREC_BF16 ? launch_fwd_rbm_t<NR_PREC_BF16, true, false>(p, a, s)
-                                  : launch_fwd_rbm_t<NR_PREC_FP16, true, false>(p, a, s);
-}
-
-int launch_bwd_rbm_input(const MlpPlan& p, const BwdrArgs& a, hipStream_t s) {
-    return p.prec == NR_PREC_BF16 ? launch_bwd_rbm_t<NR_PREC_BF16, true>(p, a, s)
-                                  : launch_bwd_rbm_t<NR_PREC_FP16, true>(p, a, s);
+int launch_bwd_rbm(const MlpPlan& p, const BwdrArgs& a, bool input_only, hipStream_t s) {
+    return dispatch_prec16(p.prec, [&](auto prec) {
+        constexpr int PREC = decltype(prec)::value;
+        return input_only ? launch_bwd_rbm_t<PREC, true>(p, a, s) : launch_bwd_rbm_t<PREC, false>(p, a, s);
+    });
 }
 
 // 16-bit g_x / g_d: one MFMA pass over the stored dz images of the x_enc-reading
 // layers and of dz_c (mlp_dinput_kernel), after the dX chain wrote them
-int input_grads16(const MlpPlan& p, const MlpSizes& z, const char* packed, const float* x, const float* d, float* g_x,
-                  float* g_d, const char* ws, int64_t M, hipStream_t s) {
+int input_grads16(const MlpPlan& p, const DinOffsets& o, const char* packed, const float* x, const float* d,
+                  float* g_x, float* g_d, const char* ws, int64_t M, hipStream_t s) {
     const int n = p.n_layers;
-    DinArgs da;
-    std::memset(&da, 0, sizeof(da));
+    DinArgs da{};
     da.packed = packed;
     da.ws = ws;
-    da.flags = reinterpret_cast<const uint8_t*>(ws + z.flags_off);
+    da.flags = reinterpret_cast<const uint8_t*>(ws + o.flags_off);
     da.x = x;
     da.d = d;
     da.g_x = g_x;
     da.g_d = g_d;
     da.M = M;
-    da.tiles = z.tiles;
+    da.tiles = o.tiles;
     da.L = p.L;
     da.Ld = p.Ld;
     da.inv_gscale = 1.0f / grad_scale(p.prec);
@@ -288,7 +261,7 @@ int input_grads16(const MlpPlan& p, const MlpSizes& z, const char* packed, const
         da.a_off[da.nsrc] = p.lin[l].pk_bwd;
         da.a_kb[da.nsrc] = p.lin[l].KB;
         da.a_p0[da.nsrc] = p.lin[l].KB - p.XB;
-        da.dz_off[da.nsrc] = z.ws_off[WS_DZ0 + l];
+        da.dz_off[da.nsrc] = o.dz_off[l];
         da.nsrc++;
     }
     // dir's W^T chunk is [feat (8) | d_enc (DB)], one chunk per dz_c block
@@ -296,8 +269,8 @@ int input_grads16(const MlpPlan& p, const MlpSizes& z, const char* packed, const
     da.dir_kb = p.lin[n + 1].KB;
     da.dir_p0 = kHB;
     da.nc = p.lin[n + 1].NB;
-    da.dz_dir_off = z.ws_off[p.ws_dir];
-    return p.prec == NR_PREC_BF16 ? launch_dinput<NR_PREC_BF16>(p, da, s) : launch_dinput<NR_PREC_FP16>(p, da, s);
+    da.dz_dir_off = o.dz_dir_off;
+    return dispatch_prec16(p.prec, [&](auto prec) { return launch_dinput<decltype(prec)::value>(p, da, s); });
 }
 
 }  // namespace nr

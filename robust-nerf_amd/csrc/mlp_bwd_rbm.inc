@@ -51,7 +51,7 @@ struct BwdrTrunkFin {
             }
         to_in_masked<PREC>(a, mw, rb, out[rb]);
         if (!OPT || keep) {  // workgroup-uniform
-            store_img<PREC>(dst, tile, kHB, rb, out[rb], 0);
+            store_img<PREC>(dst, tile, kHB, rb, out[rb]);
             nvm += 2;
         }
     }
@@ -67,7 +67,7 @@ struct BwdrFeatFin {
     __device__ __forceinline__ void operator()(int rb, f32x16& a, const bf16x8&) const {
         to_in<PREC>(a, out[rb]);
         if constexpr (STORE) {
-            store_img<PREC>(dst, tile, kHB, rb, out[rb], 0);
+            store_img<PREC>(dst, tile, kHB, rb, out[rb]);
             nvm += 2;
         }
     }
@@ -130,29 +130,11 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
     rbm_dma(s, CK_DIR);
     s.q = 0;
 
-    // heads: sigmoid / relu backward (torch: g * (1 - y) * y ; g * (y > 0))
+    // heads: sigmoid / relu backward
     float dr[3] = {0.f, 0.f, 0.f}, dzs = 0.f;
-    if (valid) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float y = a.rgb[3 * m + c];
-            dr[c] = ((a.g_rgb[3 * m + c] * (1.0f - y)) * y) * a.gscale;
-        }
-        dzs = (a.sigma[m] > 0.f ? a.g_sigma[m] : 0.f) * a.gscale;
-    }
+    head_grads(a.rgb, a.sigma, a.g_rgb, a.g_sigma, a.gscale, m, valid, dr, dzs);
     if constexpr (!INPUT) {
-        // dz of the heads as one 32-feature block: feature 0 sigma, 1..3 rgb
-        f32x16 hb;
-        zero(hb);
-        if (h == 0) {
-            hb[0] = dzs;
-            hb[1] = dr[0];
-            hb[2] = dr[1];
-            hb[3] = dr[2];
-        }
-        InBlk<PREC> hv;
-        to_in<PREC>(hb, hv);
-        store_img<PREC>(a.ws + a.ws_off[a.ws_heads], tile, 1, 0, hv, 0);
+        store_img<PREC>(a.ws + a.ws_off[a.ws_heads], tile, 1, 0, heads_blk<PREC>(h, dzs, dr));
         s.nvm += 2;
     }
     // dz_c = (W_rgb^T dz_rgb) * [h_c > 0]
@@ -171,7 +153,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_bwd_rbm_kernel(BwdrArgs a) {
                 dc[r] = h ? v[1] : v[0];
             }
             to_in_masked<PREC>(dc, mwc, nb, cin[nb]);
-            store_img<PREC>(a.ws + a.ws_off[a.ws_dir], tile, NC, nb, cin[nb], 0);
+            store_img<PREC>(a.ws + a.ws_off[a.ws_dir], tile, NC, nb, cin[nb]);
             s.nvm += 2;
         }
     }

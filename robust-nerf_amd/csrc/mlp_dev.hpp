@@ -317,7 +317,7 @@ __device__ __forceinline__ void to_in_masked(f32x16 a, const u32x4& mw, int nb, 
 // One 32-feature block of a tile as a B-operand image: FPB fragments of 1 KB.
 template <int PREC>
 __device__ __forceinline__ void store_img(char* __restrict__ region, int64_t tile, int nblk, int blk,
-                                          const InBlk<PREC>& v, int) {
+                                          const InBlk<PREC>& v) {
     // wave-uniform base (tile is per wave) + the lane's 16 B: saddr + voffset stores
     char* base = region + ((tile * nblk + blk) * kFPB<PREC>) * static_cast<int64_t>(kFragBytes) + lane16();
     if constexpr (k16<PREC>) {
@@ -335,7 +335,7 @@ __device__ __forceinline__ void store_img(char* __restrict__ region, int64_t til
 
 template <int PREC>
 __device__ __forceinline__ void load_img(const char* __restrict__ region, int64_t tile, int nblk, int blk,
-                                         InBlk<PREC>& v, int) {
+                                         InBlk<PREC>& v) {
     const char* base = region + ((tile * nblk + blk) * kFPB<PREC>) * static_cast<int64_t>(kFragBytes) + lane16();
     if constexpr (k16<PREC>) {
         v.s[0] = *reinterpret_cast<const bf16x8*>(base);
@@ -396,6 +396,52 @@ __device__ __forceinline__ f32x2 bcast2(float x) { return f32x2{x, x}; }
 // ReLU as an integer max (negative floats, -0 included, are negative as int32):
 // one v_max_i32, where the float compare-select also canonicalises its input
 __device__ __forceinline__ float relu_f(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
+
+// ---- the ends the dX chains share (mlp_bwd_kernel, mlp_bwd_rbm_kernel, mlp_dinput_kernel) ----
+// Heads backward of sample m (torch: g * (1 - y) * y for the sigmoid, g * (y > 0) for the
+// ReLU), times the loss scale.  Where !valid, dr and dzs keep the caller's values (zeros).
+__device__ __forceinline__ void head_grads(const float* rgb, const float* sigma, const float* g_rgb,
+                                           const float* g_sigma, float gscale, int64_t m, bool valid, float (&dr)[3],
+                                           float& dzs) {
+    if (valid) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float y = rgb[3 * m + c];
+            dr[c] = ((g_rgb[3 * m + c] * (1.0f - y)) * y) * gscale;
+        }
+        dzs = (sigma[m] > 0.f ? g_sigma[m] : 0.f) * gscale;
+    }
+}
+
+// dz of the heads as one 32-feature block: feature 0 sigma, 1..3 rgb (lane half h)
+template <int PREC>
+__device__ __forceinline__ InBlk<PREC> heads_blk(int h, float dzs, const float (&dr)[3]) {
+    f32x16 hb;
+    zero(hb);
+    if (h == 0) {
+        hb[0] = dzs;
+        hb[1] = dr[0];
+        hb[2] = dr[1];
+        hb[3] = dr[2];
+    }
+    InBlk<PREC> hv;
+    to_in<PREC>(hb, hv);
+    return hv;
+}
+
+// Tail of an input gradient: the two lane halves' sums added, and sample m's three
+// components stored, the loss scale divided out (store: a valid sample's lane half 0)
+__device__ __forceinline__ void store_input_grad(float* g, int64_t m, bool store, float inv_gscale, float g0,
+                                                 float g1, float g2) {
+    g0 += __shfl_xor(g0, 32);
+    g1 += __shfl_xor(g1, 32);
+    g2 += __shfl_xor(g2, 32);
+    if (store) {
+        g[3 * m] = g0 * inv_gscale;
+        g[3 * m + 1] = g1 * inv_gscale;
+        g[3 * m + 2] = g2 * inv_gscale;
+    }
+}
 
 // Active tiles of a segment from its flags (tile_flags_kernel), one wave: lane l holds
 // flag word l (tiles 4l .. 4l+3 of the segment, one byte each, 0 or 1), its count and the

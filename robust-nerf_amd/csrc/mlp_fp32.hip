@@ -108,7 +108,7 @@ struct Sink {
     int64_t tile0;
     unsigned tok;  // bit t: tile t exists
     __device__ __forceinline__ void operator()(int t, int kb, const Blk& v) const {
-        if (region != nullptr && ((tok >> t) & 1u)) store_img(region, tile0 + t, nblk, kb, v, 0);
+        if (region != nullptr && ((tok >> t) & 1u)) store_img(region, tile0 + t, nblk, kb, v);
     }
     // vector-memory stores one chunk issues (wave-uniform)
     __device__ __forceinline__ int stores() const {
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kNT, 1) void mlp_fwd_kernel(FwdArgs a) {
 #pragma unroll
                     for (int kb = 0; kb < XB; ++kb) {
                         if (tok[t])
-                            load_img(a.saved + a.sv_off[SV_XENC], tile0 + t, XB, kb, xe.v[t][kb], lane);
+                            load_img(a.saved + a.sv_off[SV_XENC], tile0 + t, XB, kb, xe.v[t][kb]);
                         else
                             xe.v[t][kb] = Blk{};
                     }
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kNT, 1) void mlp_fwd_kernel(FwdArgs a) {
                     Blk o;
                     to_in(v, o);
                     if constexpr (TRAIN)
-                        if (tok[t]) store_img(a.saved + a.sv_off[SV_XENC], tile0 + t, XB, kb, o, lane);
+                        if (tok[t]) store_img(a.saved + a.sv_off[SV_XENC], tile0 + t, XB, kb, o);
                     // constant indices: the body (accurate sinf) is too big for the
                     // pragma to unroll, and a run-time index put xe in scratch, whose
                     // reloads in the stream then drained the in-flight weight DMA
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(kNT, 1) void mlp_fwd_kernel(FwdArgs a) {
                 for (int r = 0; r < 16; ++r) v[r] = pe_feat(d0, d1, d2, 32 * kb + acc_row(r, h), a.Ld);
                 to_in(v, de.v[t][kb]);
                 if constexpr (TRAIN)
-                    if (tok[t]) store_img(a.saved + a.sv_off[a.sv_denc], tile0 + t, DB, kb, de.v[t][kb], lane);
+                    if (tok[t]) store_img(a.saved + a.sv_off[a.sv_denc], tile0 + t, DB, kb, de.v[t][kb]);
             }
         }
         stream_gemm<NC, 0, DB>(ac, dummy, 0, de, ring, st, a.sd);
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kNT, 1) void mlp_fwd_kernel(FwdArgs a) {
                 for (int nb = 0; nb < NC; ++nb) {
                     Blk v;
                     to_in(ac[t][nb], v);
-                    store_img(a.saved + a.sv_off[a.sv_hc], tile0 + t, NC, nb, v, lane);
+                    store_img(a.saved + a.sv_off[a.sv_hc], tile0 + t, NC, nb, v);
                 }
                 masks[((tile0 + t) * a.n_mask + n) * 64 + lane] = u32x4{w[t][0], w[t][1], w[t][2], w[t][3]};
             }
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(kNT, 1) void mlp_bwd_kernel(BwdArgs a) {
 #pragma unroll
     for (int t = 0; t < TPW; ++t) tok[t] = live;
     auto store_dz = [&](int wsid, int nblk, int t, int nb, const Blk& v) {
-        if (tok[t]) store_img(a.ws + a.ws_off[wsid], tile0 + t, nblk, nb, v, lane);
+        if (tok[t]) store_img(a.ws + a.ws_off[wsid], tile0 + t, nblk, nb, v);
     };
     auto mask_of = [&](int t, int layer) -> u32x4 {
         return tok[t] ? masks[((tile0 + t) * a.n_mask + layer) * 64 + lane] : u32x4{0u, 0u, 0u, 0u};
@@ -467,32 +467,12 @@ __global__ __launch_bounds__(kNT, 1) void mlp_bwd_kernel(BwdArgs a) {
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const int64_t m = (tile0 + t) * 32 + ml;
-        const bool valid = tok[t] && m < a.M;
         float dr[3] = {0.f, 0.f, 0.f};
         dzs[t] = 0.f;
-        if (valid) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float y = a.rgb[3 * m + c];
-                dr[c] = ((a.g_rgb[3 * m + c] * (1.0f - y)) * y) * a.gscale;
-            }
-            dzs[t] = (a.sigma[m] > 0.f ? a.g_sigma[m] : 0.f) * a.gscale;
-        }
-        if (tok[t]) {
-            // dz of the heads as one 32-feature block: feature 0 sigma, 1..3 rgb
-            f32x16 hb;
-            zero(hb);
-            if (h == 0) {
-                hb[0] = dzs[t];
-                hb[1] = dr[0];
-                hb[2] = dr[1];
-                hb[3] = dr[2];
-            }
-            Blk hv;
-            to_in(hb, hv);
-            store_img(a.ws + a.ws_off[a.ws_heads], tile0 + t, 1, 0, hv, lane);
-        }
-        // dz_c = (W_rgb^T dz_rgb) * [h_c > 0]
+        head_grads(a.rgb, a.sigma, a.g_rgb, a.g_sigma, a.gscale, m, tok[t] && m < a.M, dr, dzs[t]);
+        if (tok[t]) store_img(a.ws + a.ws_off[a.ws_heads], tile0 + t, 1, 0, heads_blk<kFP>(h, dzs[t], dr));
+        // dz_c = (W_rgb^T dz_rgb) * [h_c > 0]  (the rows are written out here and in
+        // mlp_bwd_rbm_kernel: through a shared helper this kernel's SGPR spills change)
         f32x16 dc[NC];
         const PImg wr0 = pimg(a.packed, a.vrgb), wr1 = pimg(a.packed, a.vrgb + NC * 128),
                    wr2 = pimg(a.packed, a.vrgb + 2 * NC * 128);
@@ -541,14 +521,7 @@ __global__ __launch_bounds__(kNT, 1) void mlp_bwd_kernel(BwdArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
                         pe_feat_bwd(d0, d1, d2, 32 * kb + acc_row(r, h), a.Ld, dd[t][kb][r], g0, g1, g2);
-                g0 += __shfl_xor(g0, 32);
-                g1 += __shfl_xor(g1, 32);
-                g2 += __shfl_xor(g2, 32);
-                if (valid && h == 0) {
-                    a.g_d[3 * m] = g0 * a.inv_gscale;
-                    a.g_d[3 * m + 1] = g1 * a.inv_gscale;
-                    a.g_d[3 * m + 2] = g2 * a.inv_gscale;
-                }
+                store_input_grad(a.g_d, m, valid && h == 0, a.inv_gscale, g0, g1, g2);
             }
         }
     }
@@ -648,6 +621,8 @@ __global__ __launch_bounds__(kNT, 1) void mlp_bwd_kernel(BwdArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
                         pe_feat_bwd(x0, x1, x2, 32 * kb + acc_row(r, h), a.L, dxe[t][kb][r], g0, g1, g2);
+                // store_input_grad's lines, written out: through the helper the XB = 1, DB = 0
+                // instance's SGPR spill count changes (profiles/mlp_args_kernel_compare.md)
                 g0 += __shfl_xor(g0, 32);
                 g1 += __shfl_xor(g1, 32);
                 g2 += __shfl_xor(g2, 32);
@@ -682,23 +657,18 @@ int launch_fwd(const MlpPlan& p, FwdArgs& a, bool train, hipStream_t s) {
     }
     const size_t lds = 2 * static_cast<size_t>(a.slot_bytes);
     const dim3 grid(static_cast<unsigned>(ceil_div_ll(a.tiles, kNT / 64))), block(kNT);
-#define NR_FWD(XB_, DB_)                                                                      \
-    if (p.XB == XB_ && p.DB == DB_) {                                                         \
-        if (train)                                                                            \
-            hipLaunchKernelGGL((mlp_fwd_kernel<XB_, DB_, true>), grid, block, lds, s, a);     \
-        else                                                                                  \
-            hipLaunchKernelGGL((mlp_fwd_kernel<XB_, DB_, false>), grid, block, lds, s, a);    \
-        return check_launch("nr_mlp_forward");                                                \
+    const bool found = dispatch_model(p, [&](auto xb, auto db) {
+        constexpr int XB = decltype(xb)::value, DB = decltype(db)::value;
+        if (train)
+            hipLaunchKernelGGL((mlp_fwd_kernel<XB, DB, true>), grid, block, lds, s, a);
+        else
+            hipLaunchKernelGGL((mlp_fwd_kernel<XB, DB, false>), grid, block, lds, s, a);
+    });
+    if (!found) {
+        set_error("nr_mlp_forward: no kernel instance for XB=%d DB=%d", p.XB, p.DB);
+        return NR_EARG;
     }
-    NR_FWD(2, 1)
-#ifndef NR_MLP_DEV  // dev builds (register/ISA inspection) compile the default model only
-    NR_FWD(2, 0)
-    NR_FWD(1, 1)
-    NR_FWD(1, 0)
-#endif
-#undef NR_FWD
-    set_error("nr_mlp_forward: no kernel instance for XB=%d DB=%d", p.XB, p.DB);
-    return NR_EARG;
+    return check_launch("nr_mlp_forward");
 }
 
 int launch_bwd(const MlpPlan& p, BwdArgs& a, bool want_x, hipStream_t s) {
@@ -711,23 +681,18 @@ int launch_bwd(const MlpPlan& p, BwdArgs& a, bool want_x, hipStream_t s) {
     const size_t lds = 2 * static_cast<size_t>(a.slot_bytes);
     // every part of every segment (select_tile's workgroup mapping)
     const dim3 grid(static_cast<unsigned>(a.nseg * (kSegTiles / (kNT / 64)))), block(kNT);
-#define NR_BWD(XB_, DB_)                                                                      \
-    if (p.XB == XB_ && p.DB == DB_) {                                                         \
-        if (want_x)                                                                           \
-            hipLaunchKernelGGL((mlp_bwd_kernel<XB_, DB_, true>), grid, block, lds, s, a);     \
-        else                                                                                  \
-            hipLaunchKernelGGL((mlp_bwd_kernel<XB_, DB_, false>), grid, block, lds, s, a);    \
-        return check_launch("nr_mlp_backward_dx");                                            \
+    const bool found = dispatch_model(p, [&](auto xb, auto db) {
+        constexpr int XB = decltype(xb)::value, DB = decltype(db)::value;
+        if (want_x)
+            hipLaunchKernelGGL((mlp_bwd_kernel<XB, DB, true>), grid, block, lds, s, a);
+        else
+            hipLaunchKernelGGL((mlp_bwd_kernel<XB, DB, false>), grid, block, lds, s, a);
+    });
+    if (!found) {
+        set_error("nr_mlp_backward_dx: no kernel instance for XB=%d DB=%d", p.XB, p.DB);
+        return NR_EARG;
     }
-    NR_BWD(2, 1)
-#ifndef NR_MLP_DEV  // dev builds (register/ISA inspection) compile the default model only
-    NR_BWD(2, 0)
-    NR_BWD(1, 1)
-    NR_BWD(1, 0)
-#endif
-#undef NR_BWD
-    set_error("nr_mlp_backward_dx: no kernel instance for XB=%d DB=%d", p.XB, p.DB);
-    return NR_EARG;
+    return check_launch("nr_mlp_backward_dx");
 }
 
 }  // namespace nr

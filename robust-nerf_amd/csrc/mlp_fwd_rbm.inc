@@ -22,7 +22,7 @@
 
 constexpr int kRbmSlot = 42 * 1024;
 // waves (tiles) per workgroup; the kernels take it as a template argument (W), the
-// launches use 8 (launch_fwd_rbm says why)
+// launches use 8 (launch_fwd_rbm_t says why)
 constexpr int kRbmWaves = 8;
 // LDS: the two ring slots, each wave's x_enc image (the skip layer's leading k
 // blocks), the head weights (w_sigma, W_rgb rows) as per-lane-half vector images
@@ -185,7 +185,7 @@ struct RbmTrunkFin {
         epi16_blk<PREC, true, TRAIN>(a, o, mw, rb);
         out[rb] = InBlk<PREC>{{o[0], o[1]}};
         if constexpr (ACT) {
-            store_img<PREC>(sv, tile, kHB, rb, out[rb], 0);
+            store_img<PREC>(sv, tile, kHB, rb, out[rb]);
             nvm += 2;
         }
         // sigma head on the fp32 activations (same FMA chain as the pair-image form)
@@ -213,7 +213,7 @@ struct RbmFeatFin {
         epi16_blk<PREC, false, false>(a, o, unused, rb);
         out[rb] = InBlk<PREC>{{o[0], o[1]}};
         if constexpr (ACT) {
-            store_img<PREC>(sv, tile, kHB, rb, out[rb], 0);
+            store_img<PREC>(sv, tile, kHB, rb, out[rb]);
             nvm += 2;
         }
     }
@@ -237,7 +237,7 @@ struct RbmDirFin {
         bf16x8 o[2];
         epi16_blk<PREC, false, TRAIN>(a, o, mw, rb);
         if constexpr (ACT) {
-            store_img<PREC>(sv, tile, NC, rb, InBlk<PREC>{{o[0], o[1]}}, 0);
+            store_img<PREC>(sv, tile, NC, rb, InBlk<PREC>{{o[0], o[1]}});
             nvm += 2;
         }
 #pragma unroll
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
     for (int kb = 0; kb < XB; ++kb) {
         *reinterpret_cast<bf16x8*>(xlds + (2 * kb) * kFragBytes + lane16()) = xe[kb].s[0];
         *reinterpret_cast<bf16x8*>(xlds + (2 * kb + 1) * kFragBytes + lane16()) = xe[kb].s[1];
-        if constexpr (ACT) store_img<PREC>(a.saved + a.sv_off[SV_XENC], tile, XB, kb, xe[kb], 0);
+        if constexpr (ACT) store_img<PREC>(a.saved + a.sv_off[SV_XENC], tile, XB, kb, xe[kb]);
     }
 
     RStream s{lds, a.packed + a.base, -1, 0, wv, kRbmSlot, W};
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(W * 64, 1) void mlp_fwd_rbm_kernel(RbmArgs a) {
                 v[r] = pe_fast(pr, 32 * kb + acc_row(r, 0), 32 * kb + acc_row(r, 1), h != 0, a.Ld);
             to_in<PREC>(v, de[kb]);
             if constexpr (ACT) {
-                store_img<PREC>(a.saved + a.sv_off[a.sv_denc], tile, DB, kb, de[kb], 0);
+                store_img<PREC>(a.saved + a.sv_off[a.sv_denc], tile, DB, kb, de[kb]);
                 s.nvm += 2;
             }
         }

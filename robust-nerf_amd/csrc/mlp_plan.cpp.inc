@@ -440,4 +440,23 @@ FrozenSizes make_frozen_sizes(const MlpPlan& p, int64_t M) {
     return f;
 }
 
+DinOffsets din_offsets(const MlpPlan& p, const MlpSizes& z) {
+    DinOffsets o{};
+    o.tiles = z.tiles;
+    o.flags_off = z.flags_off;
+    for (int l = 0; l < p.n_layers; ++l)
+        if (l == 0 || is_skip(p, l - 1)) o.dz_off[l] = z.ws_off[WS_DZ0 + l];
+    o.dz_dir_off = z.ws_off[p.ws_dir];
+    return o;
+}
+
+DinOffsets din_offsets(const MlpPlan& p, const FrozenSizes& f) {
+    DinOffsets o{};
+    o.tiles = f.tiles;
+    o.flags_off = f.flags_off;
+    for (int l = 0; l < p.n_layers; ++l) o.dz_off[l] = f.dz_off[l];  // 0 outside keep_dz
+    o.dz_dir_off = f.dz_dir_off;
+    return o;
+}
+
 }  // namespace nr

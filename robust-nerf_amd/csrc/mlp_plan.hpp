@@ -206,4 +206,17 @@ struct FrozenSizes {
 
 FrozenSizes make_frozen_sizes(const MlpPlan& p, int64_t M);
 
+// What the 16-bit input-gradient pass (mlp_dinput_kernel) reads of a workspace, in either
+// layout: the tile flags, and the dz images of the x_enc-reading trunk layers (layer 0 and
+// every layer after a skip; the other entries of dz_off are 0) and of the dir layer.
+struct DinOffsets {
+    int64_t tiles;
+    int64_t flags_off;
+    int64_t dz_off[kMaxTrunk];  // bytes, by trunk layer
+    int64_t dz_dir_off;
+};
+
+DinOffsets din_offsets(const MlpPlan& p, const MlpSizes& z);
+DinOffsets din_offsets(const MlpPlan& p, const FrozenSizes& f);  // 16-bit (fp32 has the training layout)
+
 }  // namespace nr

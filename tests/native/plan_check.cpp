@@ -9,6 +9,7 @@
 #include <vector>
 #include <set>
 #include <tuple>
+#include <utility>
 #include "mlp_plan.hpp"
 namespace nr {
 static int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -105,8 +106,52 @@ static int check_plan(const MlpPlan& p, bool say) {
         wg_bad += tot > 256 || mx != z.max_chunks;
     }
     SAY("dW workgroup plan bad %ld\n", wg_bad);
+    // what the 16-bit input-gradient pass reads of either workspace (din_offsets): equal to the
+    // fields it was built from, every offset 256-byte aligned, every image (the flags at the
+    // size the plan reserves) ending before the next region of the workspace begins, whether
+    // the pass reads that region or not
+    long din_bad = 0;
+    static std::vector<int64_t> starts;                  // where each region of the workspace begins, and its end
+    static std::vector<std::pair<int64_t, int64_t>> img;  // offset, bytes
+    auto din_check = [&](const DinOffsets& o, int64_t img_tiles, int64_t flag_bytes) {
+        img.clear();
+        for (int l = 0; l < kMaxTrunk; ++l) {
+            const bool reads = l < p.n_layers && (l == 0 || is_skip(p, l - 1));
+            if (reads) img.push_back({o.dz_off[l], img_tiles * kHidden * 32 * p.esize});
+            else din_bad += o.dz_off[l] != 0;
+        }
+        img.push_back({o.dz_dir_off, img_tiles * (kHidden / 2) * 32 * p.esize});
+        img.push_back({o.flags_off, flag_bytes});
+        for (const auto& im : img) {
+            int64_t next = -1;  // the nearest region start behind this image's (the last entry: ws_bytes)
+            for (int64_t st : starts)
+                if (st > im.first && (next < 0 || st < next)) next = st;
+            din_bad += im.first < 0 || im.first % 256 != 0 || next < 0 || im.first + im.second > next;
+        }
+    };
+    for (long M : {1L, 33L, 8193L}) {
+        const MlpSizes z = make_sizes(p, M);
+        const DinOffsets o = din_offsets(p, z);
+        din_bad += o.tiles != z.tiles || o.flags_off != z.flags_off || o.dz_dir_off != z.ws_off[p.ws_dir];
+        for (int l = 0; l < p.n_layers; ++l)
+            if (l == 0 || is_skip(p, l - 1)) din_bad += o.dz_off[l] != z.ws_off[WS_DZ0 + l];
+        starts = {z.slab_off, z.flags_off, z.blkcnt_off, z.dwlist_off, z.count_off, z.ws_bytes};
+        for (int t = 0; t < p.n_ws; ++t) starts.push_back(z.ws_off[t]);
+        din_check(o, z.tiles_alloc, z.tiles_alloc > z.nseg * kSegTiles ? z.tiles_alloc : z.nseg * kSegTiles);
+        if (p.fpb != 2) continue;  // fp32 keeps the training layout for a frozen field
+        const FrozenSizes f = make_frozen_sizes(p, M);
+        const DinOffsets q = din_offsets(p, f);
+        din_bad += q.tiles != f.tiles || q.flags_off != f.flags_off || q.dz_dir_off != f.dz_dir_off;
+        starts = {f.dz_dir_off, f.flags_off, f.blkcnt_off, f.ws_bytes};
+        for (int l = 0; l < p.n_layers; ++l) {
+            din_bad += q.dz_off[l] != f.dz_off[l] || ((f.keep_dz >> l) & 1u) != (l == 0 || is_skip(p, l - 1));
+            if ((f.keep_dz >> l) & 1u) starts.push_back(f.dz_off[l]);
+        }
+        din_check(q, f.tiles + kScratchTiles, f.nseg * kSegTiles);
+    }
+    SAY("input-gradient offsets bad %ld\n", din_bad);
 #undef SAY
-    return bad != 0 || dup != 0 || n != p.param_count || wg_bad != 0;
+    return bad != 0 || dup != 0 || n != p.param_count || wg_bad != 0 || din_bad != 0;
 }
 
 // pos_freqs 0..11, dir_freqs 0..5, depth 0..17, both view-direction settings, the three

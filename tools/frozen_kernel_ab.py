@@ -1,13 +1,14 @@
-"""Kernel-level A/B of the frozen-field MLP pair (bf16, default model) on one GPU: the saving
-forward, the masks-only forward and the inference forward; the dX stage with input gradients
-against the input-only backward; and the dW GEMM + reduce a frozen step no longer runs.
+"""Kernel-level A/B of the frozen-field MLP pair (default model; bf16, or --precision) on one
+GPU: the saving forward, the masks-only forward and the inference forward; the dX stage with
+and without input gradients against the input-only backward; and the dW GEMM + reduce a frozen
+step no longer runs.  NR_HIP_LIB selects the library, so two builds are timed in two runs.
 Raw C-ABI calls on buffers made once, HIP events around each call, the legs alternating,
 20 warm-up rounds and 200 timed ones at M = 98,304 and 786,432 (512 and 4,096 rays of 192
 fine samples).  Writes the medians and the 10th / 90th percentiles to
 profiles/frozen_kernel_ab.json (or the path given).  No CPU path.
 
-python tools/frozen_kernel_ab.py [OUT.json]"""
-import ctypes, json, statistics, sys
+python tools/frozen_kernel_ab.py [OUT.json] [--precision bf16|fp16|fp32]"""
+import argparse, ctypes, json, statistics, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path[:0] = [str(ROOT), str(ROOT / "robust-nerf_amd")]
@@ -17,9 +18,13 @@ from noisy_src._hip import call, ptr
 from noisy_src.config import ModelConfig
 from noisy_src.model import NeRF
 
+ap = argparse.ArgumentParser()
+ap.add_argument("out", nargs="?", default=str(ROOT / "profiles" / "frozen_kernel_ab.json"))
+ap.add_argument("--precision", default="bf16", choices=("bf16", "fp16", "fp32"))
+args = ap.parse_args()
 dev = "cuda"
 torch.manual_seed(0)
-net = NeRF(ModelConfig(precision="bf16")).to(dev)
+net = NeRF(ModelConfig(precision=args.precision)).to(dev)
 net._ensure_flat()
 packed = net._packed_for_forward()
 cfg = ctypes.byref(net._nr_cfg)
@@ -42,6 +47,7 @@ for M in (98304, 786432):
         "fwd_frozen": lambda: call("nr_mlp_forward_frozen", cfg, ptr(packed), ptr(net._flat), ptr(x), ptr(d), M, ptr(rgb), ptr(sigma), ptr(sv_f), st),
         "fwd_infer": lambda: call("nr_mlp_forward", cfg, ptr(packed), ptr(net._flat), ptr(x), ptr(d), M, ptr(rgb), ptr(sigma), None, st),
         "bwd_dx": lambda: call("nr_mlp_backward_dx", cfg, ptr(packed), ptr(net._flat), ptr(x), ptr(d), M, ptr(rgb), ptr(sigma), ptr(sv_t), ptr(g_rgb), ptr(g_sigma), ptr(g_x), ptr(g_d), ptr(ws_t), st),
+        "bwd_dx_noinput": lambda: call("nr_mlp_backward_dx", cfg, ptr(packed), ptr(net._flat), ptr(x), ptr(d), M, ptr(rgb), ptr(sigma), ptr(sv_t), ptr(g_rgb), ptr(g_sigma), None, None, ptr(ws_t), st),
         "bwd_input": lambda: call("nr_mlp_backward_input", cfg, ptr(packed), ptr(net._flat), ptr(x), ptr(d), M, ptr(rgb), ptr(sigma), ptr(sv_f), ptr(g_rgb), ptr(g_sigma), ptr(g_x), ptr(g_d), ptr(ws_f), st),
         "bwd_dw_reduce": lambda: (call("nr_mlp_backward_dw", cfg, M, ptr(sv_t), ptr(ws_t), st), call("nr_mlp_backward_reduce", cfg, M, ptr(ws_t), ptr(torch.empty(net._param_count, device=dev)), st)),
     }
@@ -58,7 +64,7 @@ for M in (98304, 786432):
     res = {k: {"median_ms": statistics.median(v), "p10": sorted(v)[len(v)//10], "p90": sorted(v)[9*len(v)//10]} for k, v in times.items()}
     out[M] = res
     print(M, json.dumps(res), flush=True)
-dst = Path(sys.argv[1]) if len(sys.argv) > 1 else ROOT / "profiles" / "frozen_kernel_ab.json"
+dst = Path(args.out)
 dst.parent.mkdir(parents=True, exist_ok=True)
-dst.write_text(json.dumps({"tool": "tools/frozen_kernel_ab.py", "precision": "bf16", "warmup": 20, "timed": 200,
+dst.write_text(json.dumps({"tool": "tools/frozen_kernel_ab.py", "lib": _hip.lib_path().name, "precision": args.precision, "warmup": 20, "timed": 200,
                            "unit": "ms", "results": out}, indent=1) + "\n")

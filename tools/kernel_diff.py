@@ -1,6 +1,6 @@
 """Compare the gfx950 kernels of two builds of libnerf_hip.so (CPU only).
 
-    python tools/kernel_diff.py OLD.so NEW.so [--md profiles/NAME.md]
+    python tools/kernel_diff.py OLD.so NEW.so [--md profiles/NAME.md] [--relaid PATTERN ...]
 
 For every kernel: the bytes of its function symbol, its 64-byte kernel descriptor and
 its metadata record (VGPR, AGPR, SGPR, scratch, spills, static LDS), old against new.
@@ -8,7 +8,10 @@ Kernels are matched by demangled name; the chunk-major fp32 kernels, whose templ
 lists lost their constant parameters (mlp_fwd_kernel<PREC, XB, DB, TRAIN, TPW, G, NT> ->
 <XB, DB, TRAIN>, mlp_bwd_kernel<PREC, XB, DB, TPW, G, NT, WX> -> <XB, DB, WX>), are
 matched by the parameters they kept.  Exit status 1 if a matched kernel differs or a
-kernel is missing on either side, other than those given with --gone PATTERN."""
+kernel is missing on either side, other than those given with --gone PATTERN.  A kernel
+given with --relaid PATTERN (its argument struct was laid out anew, so its kernarg offsets
+and code bytes move) passes when its VGPR, AGPR, scratch, spill and static-LDS figures
+match; its SGPR count and code size are reported."""
 
 from __future__ import annotations
 
@@ -21,6 +24,9 @@ import tempfile
 from pathlib import Path
 
 LLVM = Path("/opt/rocm/lib/llvm/bin")
+# what a kernel whose arguments were laid out anew must keep (--relaid)
+KEPT = ("vgpr_count", "agpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count",
+        "group_segment_fixed_size")
 FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count",
           "sgpr_spill_count", "group_segment_fixed_size")
 
@@ -91,6 +97,8 @@ def main() -> int:
     ap.add_argument("new")
     ap.add_argument("--md", help="write the table as markdown")
     ap.add_argument("--gone", action="append", default=[], help="regex of kernels expected only in OLD")
+    ap.add_argument("--relaid", action="append", default=[],
+                    help="regex of kernels whose code may differ while their register, scratch and LDS figures match")
     args = ap.parse_args()
     old, new = kernels(Path(args.old)), kernels(Path(args.new))
     rows, bad = [], 0
@@ -98,10 +106,11 @@ def main() -> int:
         o, n = old.get(k), new.get(k)
         if o and n:
             same = all(o.get(f) == n.get(f) for f in ("code", "kd", *FIELDS))
-            verdict = "identical" if same else "DIFFERS: " + ", ".join(
-                [f"bytes {o['bytes']} -> {n['bytes']}"] +
-                [f"{f} {o.get(f)} -> {n.get(f)}" for f in FIELDS if o.get(f) != n.get(f)])
-            bad += not same
+            what = ", ".join([f"bytes {o['bytes']} -> {n['bytes']}"] +
+                             [f"{f} {o.get(f)} -> {n.get(f)}" for f in FIELDS if o.get(f) != n.get(f)])
+            kept = any(re.search(p, k) for p in args.relaid) and all(o.get(f) == n.get(f) for f in KEPT)
+            verdict = "identical" if same else ("resources match: " if kept else "DIFFERS: ") + what
+            bad += not (same or kept)
         elif o:
             expected = any(re.search(p, k) for p in args.gone)
             verdict = "removed" if expected else "MISSING in new"
@@ -114,13 +123,15 @@ def main() -> int:
                      r.get("sgpr_count"), r.get("private_segment_fixed_size"),
                      (r.get("vgpr_spill_count") or 0) + (r.get("sgpr_spill_count") or 0),
                      r.get("group_segment_fixed_size"), verdict))
-    both = [r for r in rows if r[-1] == "identical" or r[-1].startswith("DIFFERS")]
+    both = [r for r in rows if r[-1] == "identical" or r[-1].startswith(("DIFFERS", "resources match"))]
     gone = [r for r in rows if r[-1] == "removed"]
     lines = ["| kernel | bytes | VGPR | AGPR | SGPR | scratch | spills | static LDS | old vs new |",
              "|---|---|---|---|---|---|---|---|---|"]
     lines += ["| `" + r[0] + "` | " + " | ".join(str(x) for x in r[1:]) + " |" for r in rows]
     total = (f"{len(both)} kernels in both builds, {sum(r[-1] == 'identical' for r in both)} byte-identical "
-             f"(code, kernel descriptor, metadata), {sum(r[1] for r in both)} bytes of machine code; "
+             f"(code, kernel descriptor, metadata), "
+             f"{sum(r[-1].startswith('resources match') for r in both)} with matching resources and new code, "
+             f"{sum(r[1] for r in both)} bytes of machine code; "
              f"{len(gone)} removed ({sum(r[1] for r in gone)} bytes); "
              f"{sum(r[-1] in ('ONLY in new', 'MISSING in new') for r in rows)} unmatched.")
     text = "\n".join(lines) + "\n\n" + total + "\n"
