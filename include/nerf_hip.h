@@ -465,6 +465,61 @@ int nr_composite_mse(const float* rgb, const float* sigma, const float* z,
                      float* g_sigma, float* g_rays_d, uint32_t* ticket,
                      void* workspace, nr_stream_t stream);
 
+/* ---- robust photometric losses  (no reference counterpart; additive to ABI 5)
+ * Per colour channel: d = pred - target, a scale c > 0 in colour units, q = (d/c)^2.
+ * The loss is the mean of rho(d) over the 3B channels; every rho is normalised so that
+ * rho ~ d^2 for |d| << c (c -> inf is the MSE), and rho' = 2 d w(d):
+ *   NR_LOSS_MSE            rho = d^2                            w = 1
+ *   NR_LOSS_HUBER          rho = d^2 (|d| <= c), 2c|d| - c^2    w = 1 (|d| <= c), c/|d|
+ *   NR_LOSS_CHARBONNIER    rho = 2 d^2 / (1 + sqrt(1 + q))      w = 1/sqrt(1 + q)
+ *                          (= 2c^2 (sqrt(1 + q) - 1) without the cancellation)
+ *   NR_LOSS_CAUCHY         rho = c^2 log1p(q)                   w = 1/(1 + q)
+ *   NR_LOSS_GEMAN_MCCLURE  rho = d^2 / (1 + q)                  w = 1/(1 + q)^2
+ * fp32 operation order, every operation rounded once (no contraction; / and sqrt
+ * correctly rounded):  d2 = d*d, u = d/c, q = u*u;
+ *   huber  a = |d|; a <= c: rho = d2, w = 1.0f; else rho = (2c)*a - c*c, w = c/a
+ *   charbonnier  s = sqrtf(1 + q); rho = (2*d2)/(1 + s); w = 1/s
+ *   cauchy  rho = (c*c)*log1pf(q); w = 1/(1 + q)
+ *   geman_mcclure  t = 1 + q; rho = d2/t; w = 1/(t*t)
+ * and the gradient is nr_mse_fwd_bwd's ((2*d)*(1/3B)*scale) times w -- for huber with
+ * |d| <= c, and for mse, the MSE's bits.  A ray's three rho are added as (r + g) + b.
+ *
+ * nr_robust_fwd_bwd is nr_mse_fwd_bwd for the family: loss2 (device, 2 floats,
+ * OVERWRITTEN, nullable) = {mean rho, mean d^2}, each summed in nr_mse_fwd_bwd's order;
+ * g_pred (B,3, nullable) = scale * d(mean rho)/d pred.
+ *
+ * nr_composite_robust is nr_composite_mse with the family's seed: the same contract
+ * (outputs, nullable / OVERWRITTEN / ACCUMULATED buffers, B > 0, ticket rules, one wave
+ * per ray up to 512 samples and the three separate passes beyond), plus kind and c, and
+ * loss2 = {mean rho, mean d^2} in place of the scalar loss: the second word is the plain
+ * MSE whatever is being minimised.  Gradients are bit-identical to nr_composite_fwd,
+ * nr_robust_fwd_bwd and nr_composite_bwd in sequence; with NR_LOSS_MSE every output is
+ * nr_composite_mse's and loss2[0] == loss2[1].  workspace:
+ * nr_composite_robust_workspace_bytes(B) = 20 B bytes, no initialisation needed:
+ * floats [0, B) rho per ray, [B, 2B) squared error per ray, [2B, 5B) the seed gradient
+ * of the long-ray form.  No float atomics: bit-identical from run to run.
+ * NR_EARG: kind outside the enum, c not finite or <= 0 (also under NR_LOSS_MSE, which
+ * does not read it), and the null and size cases of nr_mse_fwd_bwd / nr_composite_mse. */
+enum {
+    NR_LOSS_MSE = 0,
+    NR_LOSS_HUBER,
+    NR_LOSS_CHARBONNIER,
+    NR_LOSS_CAUCHY,
+    NR_LOSS_GEMAN_MCCLURE
+};
+int nr_robust_fwd_bwd(const float* pred, const float* target, int B, int kind,
+                      float c, float scale, float* loss2, float* g_pred,
+                      nr_stream_t stream);
+int64_t nr_composite_robust_workspace_bytes(int B);
+int nr_composite_robust(const float* rgb, const float* sigma, const float* z,
+                        const float* rays_d, const float* sigma_noise,
+                        const float* target, int B, int S, int white, int kind,
+                        float c, float grad_scale, float* rgb_map,
+                        float* depth_map, float* acc_map, float* weights,
+                        float* loss2, float* g_rgb, float* g_sigma,
+                        float* g_rays_d, uint32_t* ticket, void* workspace,
+                        nr_stream_t stream);
+
 /* ---- distortion regulariser on the ray weights  (no reference counterpart;
  *      mip-NeRF 360 eq. 15; additive to ABI 5) -------------------------------
  * weights, z (B,S): a ray's compositing weights and its sample depths, which

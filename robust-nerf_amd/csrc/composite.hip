@@ -19,9 +19,13 @@
 // Seams: gather_lane's per-sample hook (the backward computes G there, the fused kernel keeps
 // colour and z in registers); forward_sums' colour / z source (memory or those registers);
 // backward_tail's Seed and G, passed as values, so absent upstream gradients are the zeros the
-// separate kernels read.  Another photometric loss replaces only the "loss seed" lines of
-// composite_mse_ray (mse_grad and sqerr).  A wave form for longer rays is a loop around the
-// same pieces that carries E and X from one segment of 64 kCompK samples to the next.
+// separate kernels read.  The photometric loss is the "loss seed" lines of composite_mse_ray,
+// a compile-time member of the robust family (robust_weight, robust_rho):
+// composite_mse_wave_kernel is its MSE, composite_robust_wave_kernel<KIND> the others, with a
+// second loss word.  A wave form for longer rays is a loop around the same pieces that carries
+// E and X from one segment of 64 kCompK samples to the next.
+#include <cmath>
+
 #include "common.hpp"
 
 namespace nr {
@@ -345,13 +349,78 @@ __global__ __launch_bounds__(256) void composite_bwd_wave_kernel(
 
 __device__ __forceinline__ float mse_grad(float d, float inv, float scale) { return (2.0f * d) * inv * scale; }
 
-// One ray of composite_mse_wave_kernel (lane = the wave's lane).  No early return here:
-// the wave still has to reach the barriers of sum_loss_last_block.
+// ---- the photometric loss family (include/nerf_hip.h, NR_LOSS_*): per colour channel,
+// d = rgb_map - target, scale c > 0, every rho normalised to d^2 for |d| << c, and
+// rho' = 2 d w with the IRLS weight w.  fp32 operation order (tests/robust_ref.py restates
+// it; the build has no contraction, / and sqrtf are correctly rounded):
+//   d2 = d * d;  u = d / c;  q = u * u
+//   mse            rho = d2                                w = 1
+//   huber          a = |d|;  a <= c: rho = d2              w = 1.0f (literal: the MSE's bits)
+//                            else    rho = (2c) a - c c    w = c / a
+//   charbonnier    s = sqrtf(1 + q);  rho = (2 d2) / (1 + s)     w = 1 / s
+//   cauchy         rho = (c c) log1pf(q)                   w = 1 / (1 + q)
+//   geman_mcclure  t = 1 + q;  rho = d2 / t                w = 1 / (t t)
+// The seed is mse_grad(d, inv, scale) * w (no multiply at all for mse).
+// robust_weight runs in every lane (the seed), robust_rho where the loss is stored.
+template <int KIND>
+__device__ __forceinline__ float robust_q(float d, float c) {
+    const float u = d / c;
+    return u * u;
+}
+
+template <int KIND>
+__device__ __forceinline__ float robust_weight(float d, float c) {
+    static_assert(KIND >= NR_LOSS_MSE && KIND <= NR_LOSS_GEMAN_MCCLURE, "unknown loss kind");
+    if constexpr (KIND == NR_LOSS_MSE) {
+        return 1.0f;
+    } else if constexpr (KIND == NR_LOSS_HUBER) {
+        const float a = fabsf(d);
+        return a <= c ? 1.0f : c / a;
+    } else if constexpr (KIND == NR_LOSS_CHARBONNIER) {
+        return 1.0f / sqrtf(1.0f + robust_q<KIND>(d, c));
+    } else if constexpr (KIND == NR_LOSS_CAUCHY) {
+        return 1.0f / (1.0f + robust_q<KIND>(d, c));
+    } else {
+        const float t = 1.0f + robust_q<KIND>(d, c);
+        return 1.0f / (t * t);
+    }
+}
+
+template <int KIND>
+__device__ __forceinline__ float robust_rho(float d, float c) {
+    const float d2 = d * d;
+    if constexpr (KIND == NR_LOSS_MSE) {
+        return d2;
+    } else if constexpr (KIND == NR_LOSS_HUBER) {
+        const float a = fabsf(d);
+        return a <= c ? d2 : (2.0f * c) * a - c * c;
+    } else if constexpr (KIND == NR_LOSS_CHARBONNIER) {
+        return (2.0f * d2) / (1.0f + sqrtf(1.0f + robust_q<KIND>(d, c)));
+    } else if constexpr (KIND == NR_LOSS_CAUCHY) {
+        return (c * c) * log1pf(robust_q<KIND>(d, c));
+    } else {
+        return d2 / (1.0f + robust_q<KIND>(d, c));
+    }
+}
+
+// mse_grad times the weight; no multiply at all for the MSE.
+template <int KIND>
+__device__ __forceinline__ float robust_grad(float d, float c, float inv, float scale) {
+    if constexpr (KIND == NR_LOSS_MSE) return mse_grad(d, inv, scale);
+    else return mse_grad(d, inv, scale) * robust_weight<KIND>(d, c);
+}
+
+// One ray of the fused wave kernels (lane = the wave's lane).  No early return here:
+// the wave still has to reach the barriers of sum_loss_last_block.  rho_ray (the ray's
+// sum of rho) is written only when it is not NULL; composite_mse_wave_kernel passes a
+// literal NULL, so its code is the MSE's alone.
+template <int KIND>
 __device__ __forceinline__ void composite_mse_ray(const float* rgb, const float* sigma, const float* z, const float* rd,
                                                   const float* noise, const float* target, int b, int S, int K,
-                                                  int white, float inv, float scale, float* rgb_map, float* depth,
-                                                  float* acc, float* weights, float* sqerr, float* g_rgb,
-                                                  float* g_sigma, float* g_rd, int lane) {
+                                                  int white, float inv, float scale, float c, float* rgb_map,
+                                                  float* depth, float* acc, float* weights, float* sqerr,
+                                                  float* rho_ray, float* g_rgb, float* g_sigma, float* g_rd,
+                                                  int lane) {
     const Ray ray = load_ray(rd, b, S);
     const int i0 = lane * K;
     Lane ln;
@@ -362,11 +431,12 @@ __device__ __forceinline__ void composite_mse_ray(const float* rgb, const float*
     const Maps m = forward_sums(ln, E, ray, i0, S, K, white, weights, [&](int k, int64_t) { return cz[k]; });
     // loss seed
     const float d0 = m.r - target[3 * b], d1 = m.g - target[3 * b + 1], d2 = m.bl - target[3 * b + 2];
-    const Seed sd = upstream_seed(mse_grad(d0, inv, scale), mse_grad(d1, inv, scale), mse_grad(d2, inv, scale), 0.f,
-                                  0.f, white);
+    const Seed sd = upstream_seed(robust_grad<KIND>(d0, c, inv, scale), robust_grad<KIND>(d1, c, inv, scale),
+                                  robust_grad<KIND>(d2, c, inv, scale), 0.f, 0.f, white);
     if (lane == 0) {
         store_maps(m, b, rgb_map, depth, acc);
         sqerr[b] = (d0 * d0 + d1 * d1) + d2 * d2;
+        if (rho_ray) rho_ray[b] = (robust_rho<KIND>(d0, c) + robust_rho<KIND>(d1, c)) + robust_rho<KIND>(d2, c);
     }
     // backward (composite_bwd_wave_kernel with g_depth = g_acc = g_w = 0)
     float GG[kCompK];
@@ -394,9 +464,11 @@ __device__ __forceinline__ float block_sum_ordered(float v, float* part) {
 // The last workgroup to finish (an agent-scope ticket; the recipe of
 // cdna_hip_programming.md §6 Guideline 16: plain stores, release fence, relaxed
 // fetch_add, acquire fence in the reducer) sums the per-ray squared errors in a fixed
-// order and leaves the ticket at 0 for the next call.
-__device__ __forceinline__ void sum_loss_last_block(const float* sqerr, int B, float inv, unsigned* ticket,
-                                                    float* loss) {
+// order and leaves the ticket at 0 for the next call.  TWO: the robust form, which sums
+// rho_ray as well under the same ticket draw and writes loss[0..1] = {mean rho, mean d^2}.
+template <bool TWO>
+__device__ __forceinline__ void sum_loss_last_block(const float* sqerr, const float* rho_ray, int B, float inv,
+                                                    unsigned* ticket, float* loss) {
     __shared__ float part[5];  // [0..3]: wave sums, [4]: the "last" flag
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -415,6 +487,14 @@ __device__ __forceinline__ void sum_loss_last_block(const float* sqerr, int B, f
     __syncthreads();
     float sum = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) sum += sqerr[i];
+    if constexpr (TWO) {
+        __shared__ float part_rho[4];
+        float sum_rho = 0.f;
+        for (int i = threadIdx.x; i < B; i += blockDim.x) sum_rho += rho_ray[i];
+        const float tot_rho = block_sum_ordered(sum_rho, part_rho);
+        if (threadIdx.x == 0) loss[0] = tot_rho * inv;
+        ++loss;
+    }
     const float tot = block_sum_ordered(sum, part);
     if (threadIdx.x == 0) {
         *loss = tot * inv;
@@ -439,9 +519,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float* sqerr, float* g_rgb, float* g_sigma, float* g_rd, unsigned* ticket, float* loss) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (b < B) composite_mse_ray(rgb, sigma, z, rd, noise, target, b, S, K, white, inv, scale, rgb_map, depth, acc,
-                                 weights, sqerr, g_rgb, g_sigma, g_rd, lane);
-    if (ticket) sum_loss_last_block(sqerr, B, inv, ticket, loss);
+    if (b < B)
+        composite_mse_ray<NR_LOSS_MSE>(rgb, sigma, z, rd, noise, target, b, S, K, white, inv, scale, 0.f, rgb_map,
+                                       depth, acc, weights, sqerr, nullptr, g_rgb, g_sigma, g_rd, lane);
+    if (ticket) sum_loss_last_block<false>(sqerr, nullptr, B, inv, ticket, loss);
+}
+
+// The same launch with another member of the loss family in the seed (robust_grad) and
+// two loss words: loss2 = {mean rho, mean d^2}, from the per-ray sums rho_ray and sqerr.
+// NR_LOSS_MSE here writes d^2 to both arrays, so its two words are the same bits.
+template <int KIND>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void composite_robust_wave_kernel(
+    const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise, const float* target,
+    int B, int S, int K, int white, float inv, float scale, float c, float* rgb_map, float* depth, float* acc,
+    float* weights, float* sqerr, float* rho_ray, float* g_rgb, float* g_sigma, float* g_rd, unsigned* ticket,
+    float* loss2) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b < B) composite_mse_ray<KIND>(rgb, sigma, z, rd, noise, target, b, S, K, white, inv, scale, c, rgb_map, depth,
+                                       acc, weights, sqerr, rho_ray, g_rgb, g_sigma, g_rd, lane);
+    if (ticket) sum_loss_last_block<true>(sqerr, rho_ray, B, inv, ticket, loss2);
 }
 
 // loss = inv * sum of the per-ray squared errors, in a fixed order.  One block.
@@ -451,6 +548,17 @@ __global__ __launch_bounds__(1024) void loss_sum_kernel(const float* sqerr, int 
     for (int i = threadIdx.x; i < B; i += blockDim.x) s += sqerr[i];
     const float tot = block_sum_ordered(s, part);
     if (threadIdx.x == 0) *loss = tot * inv;
+}
+
+// loss2 = inv * {sum rho_ray, sum sqerr}, each in loss_sum_kernel's order.  One block.
+__global__ __launch_bounds__(1024) void loss2_sum_kernel(const float* rho_ray, const float* sqerr, int B, float inv,
+                                                         float* loss2) {
+    __shared__ float part_rho[16], part[16];
+    float sr = 0.f, s = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) sr += rho_ray[i], s += sqerr[i];
+    const float tot_rho = block_sum_ordered(sr, part_rho);
+    const float tot = block_sum_ordered(s, part);
+    if (threadIdx.x == 0) loss2[0] = tot_rho * inv, loss2[1] = tot * inv;
 }
 
 // loss = mean((p - t)^2) over n = 3B; g = 2 (p - t) / n * scale.  One block.
@@ -465,6 +573,24 @@ __global__ void mse_kernel(const float* p, const float* t, int n, float scale, f
     }
     const float tot = block_sum_ordered(s, part);
     if (threadIdx.x == 0 && loss) *loss = tot * inv;
+}
+
+// mse_kernel for the loss family: loss2 = {mean rho, mean d^2} over n = 3B (each summed in
+// mse_kernel's order), g = mse_grad * w.  One block.
+template <int KIND>
+__global__ void robust_kernel(const float* p, const float* t, int n, float c, float scale, float* loss2, float* g) {
+    __shared__ float part_rho[16], part[16];
+    float sr = 0.f, s = 0.f;
+    const float inv = 1.0f / static_cast<float>(n);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const float d = p[i] - t[i];
+        sr += robust_rho<KIND>(d, c);
+        s += d * d;
+        if (g) g[i] = robust_grad<KIND>(d, c, inv, scale);
+    }
+    const float tot_rho = block_sum_ordered(sr, part_rho);
+    const float tot = block_sum_ordered(s, part);
+    if (threadIdx.x == 0 && loss2) loss2[0] = tot_rho * inv, loss2[1] = tot * inv;
 }
 
 // Wave per ray up to 64 * kCompK samples (K per lane, four rays per workgroup), thread
@@ -565,6 +691,75 @@ int nr_mse_fwd_bwd(const float* pred, const float* target, int B, float scale, f
                        scale, loss, g);
     NR_LAUNCH_CHECK("nr_mse_fwd_bwd");
     return NR_OK;
+}
+
+// kind, launch-uniform, picks the instantiation on the host.
+#define NR_LOSS_DISPATCH(kind, LAUNCH)                               \
+    switch (kind) {                                                  \
+        case NR_LOSS_MSE: LAUNCH(NR_LOSS_MSE); break;                \
+        case NR_LOSS_HUBER: LAUNCH(NR_LOSS_HUBER); break;            \
+        case NR_LOSS_CHARBONNIER: LAUNCH(NR_LOSS_CHARBONNIER); break; \
+        case NR_LOSS_CAUCHY: LAUNCH(NR_LOSS_CAUCHY); break;          \
+        default: LAUNCH(NR_LOSS_GEMAN_MCCLURE); break;               \
+    }
+
+static bool loss_args_ok(int kind, float c) {
+    return kind >= NR_LOSS_MSE && kind <= NR_LOSS_GEMAN_MCCLURE && std::isfinite(c) && c > 0.f;
+}
+
+int nr_robust_fwd_bwd(const float* pred, const float* target, int B, int kind, float c, float scale, float* loss2,
+                      float* g, nr_stream_t stream) {
+    NR_REQUIRE(pred && target && B > 0, "nr_robust_fwd_bwd: bad arguments");
+    NR_REQUIRE(loss_args_ok(kind, c), "nr_robust_fwd_bwd: kind %d outside NR_LOSS_*, or c = %g not finite and > 0",
+               kind, static_cast<double>(c));
+#define NR_LAUNCH_ROBUST(KIND)                                                                                      \
+    hipLaunchKernelGGL(robust_kernel<KIND>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), pred, target, \
+                       3 * B, c, scale, loss2, g)
+    NR_LOSS_DISPATCH(kind, NR_LAUNCH_ROBUST)
+#undef NR_LAUNCH_ROBUST
+    NR_LAUNCH_CHECK("nr_robust_fwd_bwd");
+    return NR_OK;
+}
+
+// workspace: rho per ray (B), squared error per ray (B), the long-ray seed gradient (3B)
+int64_t nr_composite_robust_workspace_bytes(int B) { return B > 0 ? int64_t{20} * B : 0; }
+
+int nr_composite_robust(const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise,
+                        const float* target, int B, int S, int white, int kind, float c, float scale, float* rgb_map,
+                        float* depth, float* acc, float* weights, float* loss2, float* g_rgb, float* g_sigma,
+                        float* g_rd, unsigned* ticket, void* workspace, nr_stream_t stream) {
+    NR_REQUIRE(rgb && sigma && z && rd && target && rgb_map && loss2 && g_rgb && g_sigma && workspace && B > 0 && S > 0,
+               "nr_composite_robust: bad arguments");
+    NR_REQUIRE(loss_args_ok(kind, c), "nr_composite_robust: kind %d outside NR_LOSS_*, or c = %g not finite and > 0",
+               kind, static_cast<double>(c));
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    float* rho_ray = static_cast<float*>(workspace);
+    float* sqerr = rho_ray + B;
+    const float inv = 1.0f / static_cast<float>(3 * B);
+    const CompositeForm f = composite_form(B, S);
+    if (ticket && ceil_div(B, 4) > 256) ticket = nullptr;  // as nr_composite_mse
+    if (f.wave) {
+#define NR_LAUNCH_ROBUST(KIND)                                                                                     \
+    hipLaunchKernelGGL(composite_robust_wave_kernel<KIND>, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, target, \
+                       B, S, f.K, white, inv, scale, c, rgb_map, depth, acc, weights, sqerr, rho_ray, g_rgb,       \
+                       g_sigma, g_rd, ticket, loss2)
+        NR_LOSS_DISPATCH(kind, NR_LAUNCH_ROBUST)
+#undef NR_LAUNCH_ROBUST
+        NR_LAUNCH_CHECK("nr_composite_robust");
+        if (!ticket) {
+            hipLaunchKernelGGL(loss2_sum_kernel, dim3(1), dim3(1024), 0, s, rho_ray, sqerr, B, inv, loss2);
+            NR_LAUNCH_CHECK("nr_composite_robust (loss)");
+        }
+        return NR_OK;
+    }
+    // long rays: the three separate passes (the seed gradient lives in the workspace)
+    float* g_map = sqerr + B;
+    int rc = nr_composite_fwd(rgb, sigma, z, rd, noise, B, S, white, rgb_map, depth, acc, weights, stream);
+    if (rc) return rc;
+    rc = nr_robust_fwd_bwd(rgb_map, target, B, kind, c, scale, loss2, g_map, stream);
+    if (rc) return rc;
+    return nr_composite_bwd(rgb, sigma, z, rd, noise, B, S, white, g_map, nullptr, nullptr, nullptr, g_rgb, g_sigma,
+                            g_rd, stream);
 }
 
 }  // extern "C"

@@ -63,6 +63,12 @@ class NrAdamSpan(ctypes.Structure):
 NR_PREC_FP32 = 0
 NR_PREC_BF16 = 1
 NR_PREC_FP16 = 2
+# the photometric loss family (include/nerf_hip.h, the NR_LOSS_* enum)
+NR_LOSS_MSE = 0
+NR_LOSS_HUBER = 1
+NR_LOSS_CHARBONNIER = 2
+NR_LOSS_CAUCHY = 3
+NR_LOSS_GEMAN_MCCLURE = 4
 _cfg_p = ctypes.POINTER(NrMlpConfig)
 
 # name -> (restype, argtypes); mirrors include/nerf_hip.h one to one.
@@ -131,6 +137,10 @@ _SIGNATURES = {
     "nr_composite_mse": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_f, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "nr_mse_fwd_bwd": (c_i, [c_vp, c_vp, c_i, c_f, c_vp, c_vp, c_vp]),
+    "nr_robust_fwd_bwd": (c_i, [c_vp, c_vp, c_i, c_i, c_f, c_f, c_vp, c_vp, c_vp]),
+    "nr_composite_robust_workspace_bytes": (c_i64, [c_i]),
+    "nr_composite_robust": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_f, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "nr_distortion_workspace_bytes": (c_i64, [c_i]),
     "nr_distortion_loss": (c_i, [c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "nr_image_metrics_workspace_bytes": (c_i64, [c_i, c_i, c_i]),

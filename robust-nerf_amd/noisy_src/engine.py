@@ -14,6 +14,7 @@ steps live in ``graphed`` (GraphedTrainer, GraphedPoseTrainer; re-exported here)
 
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional
 
 import torch
@@ -215,6 +216,9 @@ def _loss_and_metrics(out):
     if "loss_fine" in out:
         loss = loss + out["loss_fine"]
         metrics["loss_fine"] = out["loss_fine"].detach()
+    for k in ("mse_coarse", "mse_fine"):  # a robust photometric loss: the plain MSE beside it
+        if k in out:
+            metrics[k] = out[k]
     return loss, metrics
 
 
@@ -223,6 +227,17 @@ def _check_distortion_weight(w) -> float:
     if not w >= 0.0:
         raise ValueError(f"distortion_weight must be >= 0, not {w}")
     return w
+
+
+def _check_photometric(kind, c):
+    """(kind, c) of the photometric loss: a name of ops.LOSS_KINDS and its scale in colour
+    units, finite and > 0 (checked under "mse" too, which does not use it)."""
+    if kind not in ops.LOSS_KINDS:
+        raise ValueError(f"loss must be one of {', '.join(ops.LOSS_KINDS)}, not {kind!r}")
+    c = float(c)
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"loss_scale must be finite and > 0, not {c}")
+    return kind, c
 
 
 def _distortion_term(aux, render_config, weight: float, prescale: float):
@@ -251,13 +266,19 @@ class Trainer:
     ``coarse_stream="auto"`` applies exactly that rule per step; True / False force it.
     ``distortion_weight`` > 0 adds that multiple of the distortion loss of the rendering
     network's weights (``_distortion_term``) to the loss; ``metrics["loss_distortion"]`` is
-    its unweighted mean.  At 0 the step launches nothing for it."""
+    its unweighted mean.  At 0 the step launches nothing for it.
+    ``loss`` / ``loss_scale``: the photometric loss of both networks, a name of
+    ``ops.LOSS_KINDS`` and its scale c in colour units (include/nerf_hip.h).  With a kind
+    other than "mse" the ``loss*`` metrics are the robust terms that are minimised and
+    ``mse_coarse`` / ``mse_fine`` hold the plain mean squared errors."""
 
     AUTO_COARSE_STREAM_RAYS = 1024
 
     def __init__(self, model_coarse, model_fine, render_config, lr: float = 5e-4, lr_decay: int = 250,
-                 max_norm: float = 1.0, process_group=None, coarse_stream=False, distortion_weight: float = 0.0):
+                 max_norm: float = 1.0, process_group=None, coarse_stream=False, distortion_weight: float = 0.0,
+                 loss: str = "mse", loss_scale: float = 0.1):
         self.distortion_weight = _check_distortion_weight(distortion_weight)
+        self.photometric = _check_photometric(loss, loss_scale)
         if coarse_stream not in (True, False, "auto"):
             raise ValueError(f"coarse_stream must be True, False or 'auto', not {coarse_stream!r}")
         self.coarse_stream = coarse_stream if coarse_stream == "auto" else bool(coarse_stream)
@@ -297,6 +318,8 @@ class Trainer:
             # on the coarse stream: the coarse loss's backward, beside the fine forward
             # (loss = loss_c + loss_f sends exactly d loss_c to the coarse net)
             early["loss_c"] = out_c["loss"]
+            if "mse" in out_c:
+                early["mse_c"] = out_c["mse"]
             early["loss_c"].backward(ops.unit_grad(rays_o.device))
 
         # the MSE losses (train.py:89/98) come out of the compositing (ops.composite_mse)
@@ -304,7 +327,7 @@ class Trainer:
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
                           t_rand=t_rand, u=u, return_aux=dw > 0, coarse_stream=cs,
                           coarse_backward=coarse_backward if cs is not None else None,
-                          target_rgb=target_rgb, loss_scale=gs)
+                          target_rgb=target_rgb, loss_scale=gs, photometric=self.photometric)
         dist = None
         if dw > 0:
             out, aux = out
@@ -334,6 +357,8 @@ class Trainer:
             loss.record_stream(main)
             main.wait_stream(cs)  # join the coarse chain
             metrics = {"loss_coarse": loss_c, "loss_fine": lf}
+            if "mse_c" in early:
+                metrics["mse_coarse"], metrics["mse_fine"] = early["mse_c"], out["mse_fine"]
         else:
             loss, metrics = _loss_and_metrics(out)
             if dist is None:
@@ -388,13 +413,15 @@ class PoseTrainer:
     and with them the networks' and poses' updates, are those without it, bit for bit.
 
     ``distortion_weight``: as in ``Trainer``; the term's gradient reaches the poses through the
-    rendering network like the photometric one."""
+    rendering network like the photometric one.  ``loss`` / ``loss_scale``: as in ``Trainer``."""
 
     def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,
                  lr: float = 5e-4, pose_lr: float = 1e-4, lr_decay: int = 250,
                  rotation_reg_weight: float = 0.01, translation_reg_weight: float = 0.001, process_group=None,
-                 pe_schedule=None, intrinsics=None, distortion_weight: float = 0.0):
+                 pe_schedule=None, intrinsics=None, distortion_weight: float = 0.0, loss: str = "mse",
+                 loss_scale: float = 0.1):
         self.distortion_weight = _check_distortion_weight(distortion_weight)
+        self.photometric = _check_photometric(loss, loss_scale)
         self.pe_schedule = pe_schedule
         self.model_coarse, self.model_fine = model_coarse, model_fine
         self.camera_params, self.pixel_sampler, self.render_config = camera_params, pixel_sampler, render_config
@@ -448,7 +475,8 @@ class PoseTrainer:
         # the MSE losses (train_pose_opt.py:355-370) come out of the compositing
         dw = self.distortion_weight
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
-                          t_rand=t_rand, u=u, return_aux=dw > 0, target_rgb=target, loss_scale=gs)
+                          t_rand=t_rand, u=u, return_aux=dw > 0, target_rgb=target, loss_scale=gs,
+                          photometric=self.photometric)
         if dw > 0:
             out, aux = out
         loss, metrics = _loss_and_metrics(out)
@@ -508,11 +536,13 @@ class PoseRefiner:
     w = 0, where the reference's ``theta < 1e-6`` rule gives a rotation gradient of
     exactly zero.  ``lr_decay`` (optional): the LambdaLR of the training loops.
     ``fxy`` (optional, (2,) fp32 device tensor): fixed focal lengths (fx, fy), e.g. those a
-    checkpoint learned, in place of the dataset's; the refiner does not learn intrinsics."""
+    checkpoint learned, in place of the dataset's; the refiner does not learn intrinsics.
+    ``loss`` / ``loss_scale``: the photometric loss, as in ``Trainer``."""
 
     def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,
                  pose_lr: float = 1e-3, max_norm: float = 0.1, lr_decay: Optional[int] = None,
-                 fxy: Optional[torch.Tensor] = None):
+                 fxy: Optional[torch.Tensor] = None, loss: str = "mse", loss_scale: float = 0.1):
+        self.photometric = _check_photometric(loss, loss_scale)
         self.fxy = fxy.detach() if fxy is not None else None
         if camera_params.learn_rotation and not camera_params.fixed_small_angle:
             raise ValueError("PoseRefiner needs CameraPoseParameters(fixed_small_angle=True): at w = 0 the "
@@ -549,7 +579,8 @@ class PoseRefiner:
         poses = self.camera_params.get_all_poses()
         rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses, self.fxy)
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
-                          t_rand=t_rand, u=u, target_rgb=pixel_batch.target_rgb)
+                          t_rand=t_rand, u=u, target_rgb=pixel_batch.target_rgb,
+                          photometric=self.photometric)
         loss, metrics = _loss_and_metrics(out)
         loss.backward(ops.unit_grad(loss.device))
         self.optimizer_poses.step(clip_groups=[(self.poses, self.max_norm)])

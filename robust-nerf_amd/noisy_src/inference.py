@@ -44,6 +44,7 @@ from .logger import depth_to_colormap  # the reference's inference.py:114-125 is
 from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim, image_metrics
 from .model import NeRF
 from .noise import NoiseConfig, add_noise_to_pose, compute_pose_error, set_noise_seed
+from .ops import LOSS_KINDS
 from .rendering import NeRFRenderer
 from .train import render_image
 
@@ -242,7 +243,7 @@ def checkpoint_train_poses(checkpoint_path: Path) -> torch.Tensor:
 
 def refine_view_poses(renderer: NeRFRenderer, test_data, poses: Dict[int, torch.Tensor], iters: int, lr: float = 1e-3,
                       rays_per_view: int = 256, chunk_size: int = 1024 * 4, seed: int = 0,
-                      log=print, fxy=None) -> Dict[int, torch.Tensor]:
+                      log=print, fxy=None, loss: str = "mse", loss_scale: float = 0.1) -> Dict[int, torch.Tensor]:
     """Photometric refinement of test poses on the frozen field: ``poses`` (view -> (4,4))
     are refined against their own images in groups of ``chunk_size // rays_per_view`` views,
     ``iters`` steps of ``engine.PoseRefiner`` per group with ``rays_per_view`` random pixels
@@ -250,7 +251,8 @@ def refine_view_poses(renderer: NeRFRenderer, test_data, poses: Dict[int, torch.
     noise of training (``raw_noise_std``) is off.  Every draw comes from a generator seeded
     with ``seed`` and the group's first view, so a view's result does not depend on the
     groups before it.  ``fxy`` (optional): learned focal lengths (fx, fy), used as fixed
-    values in place of ``test_data.focal``."""
+    values in place of ``test_data.focal``.  ``loss`` / ``loss_scale``: the refiner's
+    photometric loss (``engine.PoseRefiner``)."""
     import dataclasses
     from types import SimpleNamespace
 
@@ -280,7 +282,7 @@ def refine_view_poses(renderer: NeRFRenderer, test_data, poses: Dict[int, torch.
             first = last = None
             fxy_dev = torch.tensor(fxy, device=dev, dtype=torch.float32) if fxy is not None else None
             with PoseRefiner(renderer.model_coarse, renderer.model_fine, cam, sampler, rc, pose_lr=lr,
-                             fxy=fxy_dev) as refiner:
+                             fxy=fxy_dev, loss=loss, loss_scale=loss_scale) as refiner:
                 for _ in range(iters):
                     idx = base + torch.randint(0, H * W, (B,), device=dev, generator=gen)
                     img, pix, rgb = ops.gather_pixels(idx, ds.images, validate=False)
@@ -304,7 +306,8 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
                       save_images: bool = True, log=print, fused_tail: bool = False, *,
                       view_indices: Optional[Sequence[int]] = None, mode: str = "test",
                       refine_iters: int = 0, refine_lr: float = 1e-3, refine_rays_per_view: int = 256,
-                      refine_seed: int = 0, align_train_poses=None, fxy=None) -> Dict[str, object]:
+                      refine_seed: int = 0, align_train_poses=None, fxy=None, refine_loss: str = "mse",
+                      refine_loss_scale: float = 0.1) -> Dict[str, object]:
     """Reference inference.py:145-318 (same per-image records, summary keys and files),
     sharded over ``process_group``'s ranks when one is given.  ``fused_tail``: the metrics
     of a view come from ``metrics.image_metrics`` (fp64 SSIM, one read-back) and its PNGs
@@ -315,7 +318,8 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
     ``align_train_poses`` = (optimised train poses, ground-truth train poses): the test
     poses are carried into the learned frame (``pose_eval``) before the noise is drawn.
     ``refine_iters`` > 0: each rank then refines the poses of the views it renders
-    (``refine_view_poses``; no collective).  With either, every per-image record gains
+    (``refine_view_poses``; no collective) under the photometric loss ``refine_loss`` at scale
+    ``refine_loss_scale``, which the ``pose_refinement`` block records.  With either, every per-image record gains
     ``pose_rotation_error_deg_before/after`` and ``pose_translation_error_before/after``
     (against the ground truth in the frame the view is rendered in) and
     ``test_metrics.json`` a ``pose_refinement`` block; without, nothing changes.
@@ -344,7 +348,8 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
     if refine_iters > 0:
         refined = refine_view_poses(renderer, test_data, {i: views[i][0] for i in order[rank::world]}, refine_iters,
                                     lr=refine_lr, rays_per_view=refine_rays_per_view, chunk_size=chunk_size,
-                                    seed=refine_seed, log=log, fxy=fxy)
+                                    seed=refine_seed, log=log, fxy=fxy, loss=refine_loss,
+                                    loss_scale=refine_loss_scale)
     for i in order[rank::world]:
         pose, noise_info = views[i]
         pose_rec = {}
@@ -408,6 +413,7 @@ def evaluate_test_set(renderer: NeRFRenderer, test_data, output_dir: Path, noise
     if pose_eval_on:
         avg["pose_refinement"] = {
             "iters": refine_iters, "lr": refine_lr, "rays_per_view": refine_rays_per_view, "seed": refine_seed,
+            "loss": refine_loss, "loss_scale": refine_loss_scale,
             "views_per_group": max(1, chunk_size // max(1, refine_rays_per_view)),
             "aligned_train_poses": sim3 is not None, "sim3": sim3.to_json() if sim3 is not None else None,
             **{f"{k}_mean": float(np.mean([r[k] for r in per_image])) for k in (
@@ -536,6 +542,10 @@ def build_arg_parser():
     pose.add_argument("--refine_rays_per_view", type=int, default=256,
                       help="Random pixels per view and step (views are grouped chunk_size // this at a time)")
     pose.add_argument("--refine_seed", type=int, default=0, help="Seed of the refinement's pixel and sample draws")
+    pose.add_argument("--refine_loss", type=str, default="mse", choices=list(LOSS_KINDS),
+                      help="Photometric loss of the refinement (robust kernels down-weight misrendered rays)")
+    pose.add_argument("--refine_loss_scale", type=float, default=0.1,
+                      help="Scale c of a robust --refine_loss in colour units (0.1 is a choice, not a tuned value)")
     perf = ap.add_argument_group("Performance Options")
     perf.add_argument("--chunk_size", type=int, default=1024 * 4, help="Rays per chunk (default: 4096)")
     return ap
@@ -599,12 +609,14 @@ def main(argv=None) -> None:
                 log("  Test poses carried into the learned frame (Sim(3) alignment of the train poses)")
             if a.refine_poses > 0:
                 log(f"  Test-time pose refinement: {a.refine_poses} steps, lr {a.refine_lr}, "
-                    f"{a.refine_rays_per_view} rays per view")
+                    f"{a.refine_rays_per_view} rays per view"
+                    + ("" if a.refine_loss == "mse" else f", {a.refine_loss} loss (c = {a.refine_loss_scale:g})"))
             m = evaluate_test_set(renderer, test_data, output_dir, noise_config, device, a.chunk_size,
                                   process_group=pg, log=log, fused_tail=fused, view_indices=only, mode=a.mode,
                                   refine_iters=a.refine_poses, refine_lr=a.refine_lr,
                                   refine_rays_per_view=a.refine_rays_per_view, refine_seed=a.refine_seed,
-                                  align_train_poses=align, fxy=fxy)
+                                  align_train_poses=align, fxy=fxy, refine_loss=a.refine_loss,
+                                  refine_loss_scale=a.refine_loss_scale)
             log(f"\n{bar}\nTest Set Results:")
             log(f"  PSNR:  {m['psnr_mean']:.2f} ± {m['psnr_std']:.2f} dB")
             log(f"  SSIM:  {m['ssim_mean']:.4f} ± {m['ssim_std']:.4f}")

@@ -395,23 +395,31 @@ class _CompositeMSE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_map, g_depth, g_acc, g_w):
-        rgb, sigma, z, rd, nz, g_rgb, g_sigma, g_rd = ctx.saved_tensors
-        B, S = z.shape
-        if g_loss is None:
-            g_rgb, g_sigma = torch.zeros_like(g_rgb), torch.zeros_like(g_sigma)
-            g_rd = torch.zeros_like(g_rd) if g_rd is not None else None
-        elif g_loss.data_ptr() != _unit.get(g_loss.device, _NO_UNIT).data_ptr():
-            g_rgb, g_sigma = g_rgb * g_loss, g_sigma * g_loss
-            g_rd = g_rd * g_loss if g_rd is not None else None
-        if any(t is not None for t in (g_map, g_depth, g_acc, g_w)):
-            e_rgb, e_sigma = torch.empty_like(rgb), torch.empty(B, S, device=z.device, dtype=_f32)
-            e_rd = torch.zeros_like(rd) if g_rd is not None else None
-            gm = _c(g_map) if g_map is not None else torch.zeros(B, 3, device=z.device, dtype=_f32)
-            call("nr_composite_bwd", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), B, S, int(ctx.white), ptr(gm),
-                 ptr(_c(g_depth)), ptr(_c(g_acc)), ptr(_c(g_w)), ptr(e_rgb), ptr(e_sigma), ptr(e_rd), _stream())
-            g_rgb, g_sigma = g_rgb + e_rgb, g_sigma + e_sigma
-            g_rd = g_rd + e_rd if g_rd is not None else None
-        return g_rgb, g_sigma.view(ctx.sigma_shape), None, g_rd, None, None, None, None, None
+        g_rgb, g_sigma, g_rd = _composite_loss_backward(ctx, g_loss, g_map, g_depth, g_acc, g_w)
+        return g_rgb, g_sigma, None, g_rd, None, None, None, None, None
+
+
+def _composite_loss_backward(ctx, g_loss, g_map, g_depth, g_acc, g_w):
+    """The backward of the fused compositing, whichever photometric loss seeded it: the
+    stored gradient of the loss times ``g_loss``, plus a composite backward of their own
+    for gradients arriving at the other outputs."""
+    rgb, sigma, z, rd, nz, g_rgb, g_sigma, g_rd = ctx.saved_tensors
+    B, S = z.shape
+    if g_loss is None:
+        g_rgb, g_sigma = torch.zeros_like(g_rgb), torch.zeros_like(g_sigma)
+        g_rd = torch.zeros_like(g_rd) if g_rd is not None else None
+    elif g_loss.data_ptr() != _unit.get(g_loss.device, _NO_UNIT).data_ptr():
+        g_rgb, g_sigma = g_rgb * g_loss, g_sigma * g_loss
+        g_rd = g_rd * g_loss if g_rd is not None else None
+    if any(t is not None for t in (g_map, g_depth, g_acc, g_w)):
+        e_rgb, e_sigma = torch.empty_like(rgb), torch.empty(B, S, device=z.device, dtype=_f32)
+        e_rd = torch.zeros_like(rd) if g_rd is not None else None
+        gm = _c(g_map) if g_map is not None else torch.zeros(B, 3, device=z.device, dtype=_f32)
+        call("nr_composite_bwd", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), B, S, int(ctx.white), ptr(gm),
+             ptr(_c(g_depth)), ptr(_c(g_acc)), ptr(_c(g_w)), ptr(e_rgb), ptr(e_sigma), ptr(e_rd), _stream())
+        g_rgb, g_sigma = g_rgb + e_rgb, g_sigma + e_sigma
+        g_rd = g_rd + e_rd if g_rd is not None else None
+    return g_rgb, g_sigma.view(ctx.sigma_shape), g_rd
 
 
 def composite_mse(rgb, sigma, z_vals, rays_d, target, noise=None, white_background=True, grad_scale=1.0,
@@ -424,6 +432,67 @@ def composite_mse(rgb, sigma, z_vals, rays_d, target, noise=None, white_backgrou
     sig = sigma.reshape(z_vals.shape)
     return _CompositeMSE.apply(rgb, sig, z_vals, rays_d, noise, target, bool(white_background), float(grad_scale),
                                ticket)
+
+
+# The photometric loss family, in the order of the header's NR_LOSS_* enum.
+LOSS_KINDS = ("mse", "huber", "charbonnier", "cauchy", "geman_mcclure")
+
+
+def loss_kind_index(kind: str) -> int:
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"loss kind must be one of {', '.join(LOSS_KINDS)}, got {kind!r}")
+    return LOSS_KINDS.index(kind)
+
+
+class _CompositeLoss(torch.autograd.Function):
+    """_CompositeMSE with a member of the robust loss family in the seed
+    (nr_composite_robust): outputs (loss, mse, rgb_map, depth, acc, weights), where
+    ``loss`` is the mean of rho and ``mse`` the plain mean squared error of the same
+    rgb_map, not differentiable."""
+
+    @staticmethod
+    def forward(ctx, rgb, sigma, z, rays_d, noise, target, white, grad_scale, ticket, kind, c):
+        rgb, sigma, z, rd, tgt = _c(rgb), _c(sigma), _c(z), _c(rays_d), _c(target)
+        B, S = z.shape
+        nz = _c(noise)
+        dev = z.device
+        rgb_map = torch.empty(B, 3, device=dev, dtype=_f32)
+        depth = torch.empty(B, device=dev, dtype=_f32)
+        acc = torch.empty(B, device=dev, dtype=_f32)
+        weights = torch.empty(B, S, device=dev, dtype=_f32)
+        loss2 = torch.empty(2, device=dev, dtype=_f32)
+        g_rgb = torch.empty_like(rgb)
+        g_sigma = torch.empty(B, S, device=dev, dtype=_f32)
+        g_rd = torch.zeros_like(rd) if ctx.needs_input_grad[3] else None
+        ws = torch.empty(max(16, int(_hip.load().nr_composite_robust_workspace_bytes(B))), device=dev,
+                         dtype=torch.uint8)
+        call("nr_composite_robust", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), ptr(tgt), B, S, int(white),
+             int(kind), float(c), float(grad_scale), ptr(rgb_map), ptr(depth), ptr(acc), ptr(weights), ptr(loss2),
+             ptr(g_rgb), ptr(g_sigma), ptr(g_rd), ptr(ticket), ptr(ws), _stream())
+        ctx.save_for_backward(rgb, sigma, z, rd, nz, g_rgb, g_sigma, g_rd)
+        ctx.white = white
+        ctx.sigma_shape = sigma.shape
+        ctx.set_materialize_grads(False)
+        loss, mse = loss2[0], loss2[1]
+        ctx.mark_non_differentiable(mse)
+        return loss, mse, rgb_map, depth, acc, weights
+
+    @staticmethod
+    def backward(ctx, g_loss, g_mse, g_map, g_depth, g_acc, g_w):
+        g_rgb, g_sigma, g_rd = _composite_loss_backward(ctx, g_loss, g_map, g_depth, g_acc, g_w)
+        return g_rgb, g_sigma, None, g_rd, None, None, None, None, None, None, None
+
+
+def composite_loss(rgb, sigma, z_vals, rays_d, target, kind, c, noise=None, white_background=True, grad_scale=1.0,
+                   ticket=None):
+    """``composite_mse`` with the photometric loss ``kind`` (one of LOSS_KINDS) at scale
+    ``c`` (colour units, > 0): returns (loss, mse, rgb_map, depth, acc, weights).  ``loss``
+    is the mean of rho over the 3B channels and carries the gradient (times ``grad_scale``);
+    ``mse`` is the plain mean squared error of the same rgb_map, detached."""
+    _check(rgb, sigma, z_vals, rays_d, target, noise, ticket)
+    sig = sigma.reshape(z_vals.shape)
+    return _CompositeLoss.apply(rgb, sig, z_vals, rays_d, noise, target, bool(white_background), float(grad_scale),
+                                ticket, loss_kind_index(kind), float(c))
 
 
 # ---------------------------------------------------------------- A3 / A4 ----
@@ -644,6 +713,42 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) 
     """The loss value is always the plain mean; only its gradient carries ``grad_scale``."""
     _check(pred, target)
     return _MSE.apply(pred, target, float(grad_scale))
+
+
+def robust_loss_and_grad(pred, target, kind, c, scale=1.0):
+    """(loss2 = {mean rho, mean (pred-target)^2} (device), d mean rho/d pred * scale) for the
+    loss ``kind`` at scale ``c`` (nr_robust_fwd_bwd)."""
+    _check(pred, target)
+    p, t = _c(pred), _c(target)
+    loss2 = torch.empty(2, device=p.device, dtype=_f32)
+    g = torch.empty_like(p)
+    call("nr_robust_fwd_bwd", ptr(p), ptr(t), p.shape[0], loss_kind_index(kind), float(c), float(scale), ptr(loss2),
+         ptr(g), _stream())
+    return loss2, g
+
+
+class _Robust(torch.autograd.Function):
+    """_MSE for the robust loss family: the mean of rho(pred - target)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind, c, grad_scale):
+        loss2, g = robust_loss_and_grad(pred, target, kind, c, grad_scale)
+        ctx.save_for_backward(g)
+        return loss2[0]
+
+    @staticmethod
+    def backward(ctx, gl):
+        (g,) = ctx.saved_tensors
+        if gl.data_ptr() == _unit.get(gl.device, _NO_UNIT).data_ptr():
+            return g, None, None, None, None
+        return g * gl, None, None, None, None
+
+
+def robust_loss(pred: torch.Tensor, target: torch.Tensor, kind: str, c: float, scale: float = 1.0) -> torch.Tensor:
+    """``mse_loss`` with the photometric loss ``kind`` (one of LOSS_KINDS) at scale ``c``; the
+    value is the plain mean of rho, only its gradient carries ``scale``."""
+    _check(pred, target)
+    return _Robust.apply(pred, target, kind, float(c), float(scale))
 
 
 class _Distortion(torch.autograd.Function):

@@ -9,7 +9,7 @@ sampling -> fused MLP -> composite exactly as rendering.py:119-240 does, and
 
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -40,9 +40,12 @@ def raw2outputs(rgb: torch.Tensor, sigma: torch.Tensor, z_vals: torch.Tensor, ra
     }
 
 
-def _outputs(rgb, sigma, z_vals, rays_d, raw_noise_std, white_background, target_rgb, loss_scale, net=None):
+def _outputs(rgb, sigma, z_vals, rays_d, raw_noise_std, white_background, target_rgb, loss_scale, net=None,
+             photometric=None):
     """raw2outputs, or with a target its training form fused with the MSE loss (one
-    launch, summing the loss with ``net``'s ticket; the dict then also holds "loss")."""
+    launch, summing the loss with ``net``'s ticket; the dict then also holds "loss").
+    ``photometric``: (kind, c) of ops.LOSS_KINDS; with a kind other than "mse" the loss is
+    that robust term (ops.composite_loss) and the dict also holds the plain "mse"."""
     if target_rgb is None:
         return raw2outputs(rgb, sigma, z_vals, rays_d, raw_noise_std=raw_noise_std,
                            white_background=white_background)
@@ -50,11 +53,19 @@ def _outputs(rgb, sigma, z_vals, rays_d, raw_noise_std, white_background, target
     noise = None
     if raw_noise_std > 0.0:
         noise = torch.randn(*z_vals.shape[:-1], S, device=z_vals.device) * raw_noise_std
+    ticket = net.loss_ticket(z_vals.device) if hasattr(net, "loss_ticket") else None
+    if photometric is not None and photometric[0] != "mse":
+        loss, mse, rgb_map, depth, acc, weights = ops.composite_loss(
+            rgb.reshape(-1, S, 3), sigma.reshape(-1, S), z_vals.reshape(-1, S), rays_d.reshape(-1, 3), target_rgb,
+            photometric[0], photometric[1], noise=None if noise is None else noise.reshape(-1, S),
+            white_background=white_background, grad_scale=loss_scale, ticket=ticket)
+        return {"rgb_map": rgb_map, "depth_map": depth, "acc_map": acc, "weights": weights, "loss": loss,
+                "mse": mse}
     loss, rgb_map, depth, acc, weights = ops.composite_mse(
         rgb.reshape(-1, S, 3), sigma.reshape(-1, S), z_vals.reshape(-1, S), rays_d.reshape(-1, 3), target_rgb,
         noise=None if noise is None else noise.reshape(-1, S), white_background=white_background,
         grad_scale=loss_scale,
-        ticket=net.loss_ticket(z_vals.device) if hasattr(net, "loss_ticket") else None)
+        ticket=ticket)
     return {"rgb_map": rgb_map, "depth_map": depth, "acc_map": acc, "weights": weights, "loss": loss}
 
 
@@ -63,8 +74,8 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
                 u: Optional[torch.Tensor] = None, return_aux: bool = False,
                 coarse_stream: Optional[torch.cuda.Stream] = None,
                 coarse_backward: Optional[Callable[[Dict[str, torch.Tensor]], None]] = None,
-                target_rgb: Optional[torch.Tensor] = None, loss_scale: float = 1.0
-                ) -> Dict[str, torch.Tensor]:
+                target_rgb: Optional[torch.Tensor] = None, loss_scale: float = 1.0,
+                photometric: Optional[Tuple[str, float]] = None) -> Dict[str, torch.Tensor]:
     """Reference rendering.py:119-240.  ``t_rand`` / ``u`` inject the jitter and
     inverse-CDF uniforms (otherwise drawn with torch.rand as the reference does).
 
@@ -80,7 +91,12 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
 
     ``target_rgb`` (B,3), training: the MSE losses of train.py:89/98 are computed with the
     compositing (ops.composite_mse: one pass that also prepares the backward) and returned
-    as "loss_coarse" / "loss_fine"; their gradients carry ``loss_scale``."""
+    as "loss_coarse" / "loss_fine"; their gradients carry ``loss_scale``.
+
+    ``photometric``: None or (kind, c), the photometric loss of ops.LOSS_KINDS and its scale
+    in colour units.  None or kind "mse" is the path above; otherwise "loss_coarse" /
+    "loss_fine" are the robust terms (ops.composite_loss) and "mse_coarse" / "mse_fine", the
+    plain mean squared errors of the same maps, are returned beside them."""
     perturb = config.perturb if is_train else False
     raw_noise_std = config.raw_noise_std if is_train else 0.0
     N_rays = rays_o.shape[0]
@@ -102,7 +118,8 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
         with torch.cuda.stream(coarse_stream):
             rgb_c, sigma_c = model_coarse(pts.reshape(-1, 3), vd)
             out_c = _outputs(rgb_c.reshape(N_rays, Nc, 3), sigma_c.reshape(N_rays, Nc, 1), z_c, rays_d,
-                             raw_noise_std, config.white_background, target_rgb, loss_scale, model_coarse)
+                             raw_noise_std, config.white_background, target_rgb, loss_scale, model_coarse,
+                             photometric)
             if coarse_backward is not None:
                 forward_done = coarse_stream.record_event()
                 coarse_backward(out_c)
@@ -113,7 +130,8 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
     else:
         rgb_c, sigma_c = model_coarse(pts.reshape(-1, 3), vd)
         out_c = _outputs(rgb_c.reshape(N_rays, Nc, 3), sigma_c.reshape(N_rays, Nc, 1), z_c, rays_d,
-                         raw_noise_std, config.white_background, target_rgb, loss_scale, model_coarse)
+                         raw_noise_std, config.white_background, target_rgb, loss_scale, model_coarse,
+                         photometric)
     results = {
         "rgb_coarse": out_c["rgb_map"],
         "depth_coarse": out_c["depth_map"],
@@ -121,6 +139,8 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
     }
     if "loss" in out_c:
         results["loss_coarse"] = out_c["loss"]
+    if "mse" in out_c:
+        results["mse_coarse"] = out_c["mse"]
     aux = {"z_coarse": z_c, "weights_coarse": out_c["weights"]}
     if config.use_hierarchical and model_fine is not None:
         Nf = config.num_samples_fine
@@ -132,9 +152,12 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
         T = z_f.shape[-1]
         rgb_f, sigma_f = model_fine(pts_f.reshape(-1, 3), vd_f)
         out_f = _outputs(rgb_f.reshape(N_rays, T, 3), sigma_f.reshape(N_rays, T, 1), z_f, rays_d,
-                         raw_noise_std, config.white_background, target_rgb, loss_scale, model_fine)
+                         raw_noise_std, config.white_background, target_rgb, loss_scale, model_fine,
+                         photometric)
         if "loss" in out_f:
             results["loss_fine"] = out_f["loss"]
+        if "mse" in out_f:
+            results["mse_fine"] = out_f["mse"]
         results["rgb_fine"] = out_f["rgb_map"]
         results["depth_fine"] = out_f["depth_map"]
         results["acc_fine"] = out_f["acc_map"]

@@ -29,6 +29,7 @@ from .logger import ExperimentLogger, TrainingMetrics, ValidationMetrics
 from .metrics import LPIPSMetric, compute_mse, compute_psnr, compute_ssim
 from .model import create_nerf
 from .noise import NoiseConfig
+from .ops import LOSS_KINDS
 
 
 def set_seed(seed: int) -> None:
@@ -145,7 +146,8 @@ class IterationLog:
              extra_scalars: Optional[Dict[str, torch.Tensor]] = None, meta=None) -> None:
         """Queue this iteration's losses (and ``extra_scalars``, device scalars as well);
         write the previous iteration's row."""
-        keys = ["loss", "loss_coarse"] + [k for k in ("loss_fine", "loss_distortion") if k in metrics]
+        keys = ["loss", "loss_coarse"] + [k for k in ("loss_fine", "loss_distortion", "mse_coarse", "mse_fine")
+                                          if k in metrics]
         vals = [metrics[k] for k in keys]
         if extra_scalars:
             keys += extra_scalars
@@ -171,7 +173,8 @@ class IterationLog:
             return
         vals, (it, keys, lr, batch_time, meta) = done
         vm = dict(zip(keys, vals))
-        last = vm.get("loss_fine", vm["loss_coarse"])
+        # under a robust photometric loss the plain MSE rides along (mse_*): a PSNR stays a PSNR
+        last = vm.get("mse_fine", vm.get("mse_coarse", vm.get("loss_fine", vm["loss_coarse"])))
         psnr = -10.0 * math.log10(last) if last > 0 else float("inf")
         rays_per_sec = self.batch_size / batch_time
         self.logger.log_training(TrainingMetrics(iteration=it, loss=vm["loss"], loss_coarse=vm["loss_coarse"],
@@ -279,6 +282,12 @@ COMMON_ARGS = {
     "distortion_weight": dict(type=float, default=0.0,
                               help="weight of the distortion regulariser on the rendering network's ray weights "
                                    "(mip-NeRF 360; 0 = off, 0.01 is the paper's)"),
+    "loss": dict(type=str, default="mse", choices=list(LOSS_KINDS),
+                 help="photometric loss per colour channel (robust kernels down-weight rays that a wrong pose "
+                      "lands on the wrong surface; the logged PSNR is always the plain MSE's)"),
+    "loss_scale": dict(type=float, default=0.1,
+                       help="scale c of a robust --loss in colour units: where it stops being quadratic (0.1 is a "
+                            "choice, a tenth of the colour range, not a tuned value)"),
 }
 
 
@@ -288,6 +297,11 @@ def add_common_args(ap, names: str, **overrides) -> None:
     ``add_argument`` keywords that replace the table's (a default, a help text)."""
     for name in names.split():
         ap.add_argument(f"--{name}", **{**COMMON_ARGS[name], **overrides.get(name, {})})
+
+
+def loss_line(loss: str, loss_scale: float) -> str:
+    """The console line's note of a robust photometric loss ("" under the MSE)."""
+    return "" if loss == "mse" else f"{loss}(c={loss_scale:g}) | "
 
 
 def noise_config_from_args(a) -> Optional[NoiseConfig]:
@@ -328,5 +342,5 @@ def run_cli(a, run_name: Callable, call: Callable) -> None:
 
 __all__ = ["set_seed", "Run", "open_run", "create_nerf_for", "noise_dict", "NO_NOISE", "write_experiment_config",
            "draw_randoms", "slice_for_rank", "IterationLog", "due", "evaluate_views", "checkpoint_config",
-           "base_checkpoint", "write_checkpoint", "COMMON_ARGS", "add_common_args", "noise_config_from_args",
-           "nerf_config_from_args", "run_cli"]
+           "base_checkpoint", "write_checkpoint", "COMMON_ARGS", "add_common_args", "loss_line",
+           "noise_config_from_args", "nerf_config_from_args", "run_cli"]

@@ -43,8 +43,8 @@ from .optim import FusedAdam, clip_grad_norm_
 from .rays import get_ray_directions, get_rays
 from .rendering import NeRFRenderer
 from .run import (NO_NOISE, IterationLog, add_common_args, base_checkpoint, checkpoint_config,  # noqa: F401
-                  create_nerf_for, draw_randoms, due, evaluate_views, noise_dict, open_run, run_cli, set_seed,
-                  slice_for_rank, write_checkpoint, write_experiment_config)
+                  create_nerf_for, draw_randoms, due, evaluate_views, loss_line, noise_dict, open_run, run_cli,
+                  set_seed, slice_for_rank, write_checkpoint, write_experiment_config)
 
 
 def generate_experiment_name(scene: str, noise_config: Optional[NoiseConfig], base_name: str = "") -> str:
@@ -140,7 +140,7 @@ def load_checkpoint(checkpoint_path, model_coarse, model_fine, optimizer: Option
 def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
           train_data: Optional[BlenderData] = None, val_data: Optional[BlenderData] = None,
           process_group=None, log=print, graph: bool = False,
-          distortion_weight: float = 0.0) -> Dict[str, object]:
+          distortion_weight: float = 0.0, loss: str = "mse", loss_scale: float = 0.1) -> Dict[str, object]:
     """Reference train.py:307-577.  ``train_data`` / ``val_data`` (optional) replace the
     on-disk scene; ``process_group`` (or a torchrun environment, see ``main``) makes it
     data parallel.  ``graph`` replays the training step from a hipGraph after the first
@@ -148,6 +148,10 @@ def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
     the RCCL all-reduces are captured into it too (``nccl`` backend only).
     ``distortion_weight`` > 0 adds that multiple of the distortion loss on the rendering
     network's ray weights (``engine.Trainer``); it is logged on the console line only.
+    ``loss`` / ``loss_scale`` (``--loss``, ``--loss_scale``): the photometric loss of both
+    networks and its scale (``engine.Trainer``).  With a robust kind the CSV's loss columns
+    are what is minimised, its ``psnr`` column stays the plain MSE's and the console line
+    names the kind.
     Returns the networks, the output directory and the final metrics."""
     import torch.distributed as dist
 
@@ -166,18 +170,20 @@ def train(config: NeRFConfig, noise_config: Optional[NoiseConfig] = None, *,
     # coarse_stream="auto": the coarse chain becomes a second graph branch only in a
     # --graph replay of <= 1024 rays (engine.Trainer), where it pays
     trainer = Trainer(model_coarse, model_fine, config.render, lr=config.train.lr, lr_decay=config.train.lr_decay,
-                      process_group=process_group, coarse_stream="auto", distortion_weight=distortion_weight)
+                      process_group=process_group, coarse_stream="auto", distortion_weight=distortion_weight,
+                      loss=loss, loss_scale=loss_scale)
     optimizer = trainer.optimizer
     if rank == 0:
         write_experiment_config(output_dir, config, exp_name, world, noise_config, NO_NOISE,
                                 after_batch={"img_scale": config.data.img_scale},
-                                extra={"distortion_weight": distortion_weight})
+                                extra={"distortion_weight": distortion_weight, "loss": loss,
+                                       "loss_scale": loss_scale})
         log(f"NeRF training: {exp_name} -> {output_dir} ({world} rank(s), {sampler.n_rays:,} rays, "
             f"{train_data.H}x{train_data.W}, focal {train_data.focal:.2f})")
 
     def line(vm, lr, rays_per_sec, meta):
         dist_part = f"distortion: {vm['loss_distortion']:.5f} | " if "loss_distortion" in vm else ""
-        return f"{dist_part}lr: {lr:.2e} | rays/s: {rays_per_sec:.0f}"
+        return f"{loss_line(loss, loss_scale)}{dist_part}lr: {lr:.2e} | rays/s: {rays_per_sec:.0f}"
 
     B = config.data.batch_size
     best_psnr = 0.0
@@ -256,9 +262,18 @@ def build_arg_parser():
     return ap
 
 
+def build_cli_parser():
+    """The command line's parser: ``build_arg_parser()`` (the reference's flags and this
+    project's earlier ones, in the order its callers rely on) plus the photometric loss
+    flags ``--loss`` and ``--loss_scale``."""
+    ap = build_arg_parser()
+    add_common_args(ap, "loss loss_scale")
+    return ap
+
+
 def main(argv=None) -> None:
     """``python -m noisy_src.train`` (or under ``torchrun`` for data parallelism)."""
-    a = build_arg_parser().parse_args(argv)
+    a = build_cli_parser().parse_args(argv)
 
     def run_name(noise_config, world):  # a single process leaves "auto" to train()
         auto = world > 1 and a.exp_name in ("auto", "")
@@ -266,7 +281,8 @@ def main(argv=None) -> None:
 
     def call(cfg, noise_config, pg, name):
         cfg.train.experiment_name = name
-        train(cfg, noise_config, process_group=pg, graph=a.graph, distortion_weight=a.distortion_weight)
+        train(cfg, noise_config, process_group=pg, graph=a.graph, distortion_weight=a.distortion_weight, loss=a.loss,
+              loss_scale=a.loss_scale)
 
     run_cli(a, run_name, call)
 

@@ -60,7 +60,7 @@ from .noise import NoiseConfig, add_noise_to_poses, compute_pose_error
 from .optim import FusedAdam, clip_grad_norm_
 from .rendering import NeRFRenderer, render_rays
 from .run import (IterationLog, add_common_args, base_checkpoint, create_nerf_for, draw_randoms, due,  # noqa: F401
-                  evaluate_views, open_run, run_cli, set_seed, slice_for_rank, write_checkpoint,
+                  evaluate_views, loss_line, open_run, run_cli, set_seed, slice_for_rank, write_checkpoint,
                   write_experiment_config)
 from .train import render_image
 
@@ -319,7 +319,8 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                  process_group=None, experiment_name: Optional[str] = None,
                                  log=print, graph: bool = False, c2f: Optional[Tuple[float, float]] = None,
                                  fixed_small_angle: bool = False, learn_focal: Optional[str] = None,
-                                 focal_init_scale: float = 1.0, distortion_weight: float = 0.0) -> Dict[str, object]:
+                                 focal_init_scale: float = 1.0, distortion_weight: float = 0.0,
+                                 loss: str = "mse", loss_scale: float = 0.1) -> Dict[str, object]:
     """Reference train_pose_opt.py:613-1054 (same arguments, outputs and files).
     ``train_data`` / ``val_data`` (optional) replace the on-disk scene; ``process_group``
     makes it data parallel; ``experiment_name`` pins the generated run name (all ranks).
@@ -340,7 +341,10 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     ``*_focal`` entries.  None (the default) is the reference's fixed focal length.
     ``distortion_weight`` > 0 (``--distortion_weight``) adds that multiple of the distortion
     loss on the rendering network's ray weights (``engine.PoseTrainer``); its value goes to
-    the console line only."""
+    the console line only.
+    ``loss`` / ``loss_scale`` (``--loss``, ``--loss_scale``): the photometric loss of both
+    networks and its scale (``engine.PoseTrainer``); the CSV's ``psnr`` stays the plain
+    MSE's and the console line names a robust kind."""
     import torch.distributed as dist
 
     pe_schedule = None
@@ -383,7 +387,8 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     trainer = PoseTrainer(model_coarse, model_fine, camera_params, pixel_sampler, config.render, lr=config.train.lr,
                           pose_lr=pose_lr, lr_decay=config.train.lr_decay, rotation_reg_weight=rotation_reg_weight,
                           translation_reg_weight=translation_reg_weight, process_group=process_group,
-                          pe_schedule=pe_schedule, intrinsics=intrinsics, distortion_weight=distortion_weight)
+                          pe_schedule=pe_schedule, intrinsics=intrinsics, distortion_weight=distortion_weight,
+                          loss=loss, loss_scale=loss_scale)
     optimizer_nerf, optimizer_poses = trainer.optimizer_nerf, trainer.optimizer_poses
     if rank == 0:
         extra = {}
@@ -394,6 +399,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         if intrinsics is not None:
             extra["learn_focal"] = {"mode": learn_focal, "focal_init_scale": focal_init_scale}
         extra["distortion_weight"] = distortion_weight
+        extra["loss"], extra["loss_scale"] = loss, loss_scale
         write_experiment_config(output_dir, config, exp_name, world, noise_config, extra=extra, after_name={
             "init_mode": init_mode,
             "pose_optimization": {"learn_rotation": learn_rotation, "learn_translation": learn_translation,
@@ -406,7 +412,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         focal = f" | focal err: {vm['focal_error_pct']:.3f}%" if "focal_error_pct" in vm else ""
         if "loss_distortion" in vm:
             focal += f" | distortion: {vm['loss_distortion']:.5f}"
-        return f"lr: {lr:.2e} | poses: {'optimizing' if optimizing else 'frozen'}{focal}"
+        return f"{loss_line(loss, loss_scale)}lr: {lr:.2e} | poses: {'optimizing' if optimizing else 'frozen'}{focal}"
 
     def learned_fxy():
         return intrinsics.fxy_values() if intrinsics is not None else None
@@ -534,9 +540,18 @@ def build_arg_parser():
     return ap
 
 
+def build_cli_parser():
+    """The command line's parser: ``build_arg_parser()`` (the reference's flags and this
+    project's earlier ones, in the order its callers rely on) plus the photometric loss
+    flags ``--loss`` and ``--loss_scale``."""
+    ap = build_arg_parser()
+    add_common_args(ap, "loss loss_scale")
+    return ap
+
+
 def main(argv=None) -> None:
     """``python -m noisy_src.train_pose_opt`` (or under ``torchrun`` for data parallelism)."""
-    a = build_arg_parser().parse_args(argv)
+    a = build_cli_parser().parse_args(argv)
 
     def call(cfg, noise_config, pg, name):
         train_with_pose_optimization(cfg, noise_config, a.init_mode, a.pose_lr, a.pose_opt_delay,
@@ -544,7 +559,8 @@ def main(argv=None) -> None:
                                      a.translation_reg_weight, process_group=pg, experiment_name=name,
                                      graph=a.graph, c2f=tuple(a.c2f) if a.c2f is not None else None,
                                      fixed_small_angle=a.fixed_small_angle, learn_focal=a.learn_focal,
-                                     focal_init_scale=a.focal_init_scale, distortion_weight=a.distortion_weight)
+                                     focal_init_scale=a.focal_init_scale, distortion_weight=a.distortion_weight,
+                                     loss=a.loss, loss_scale=a.loss_scale)
 
     run_cli(a, lambda noise_config, world: generate_experiment_name(a.scene, noise_config, a.init_mode), call)
 
