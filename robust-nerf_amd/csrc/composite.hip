@@ -24,6 +24,8 @@
 // composite_mse_wave_kernel is its MSE, composite_robust_wave_kernel<KIND> the others, with a
 // second loss word.  A wave form for longer rays is a loop around the same pieces that carries
 // E and X from one segment of 64 kCompK samples to the next.
+// Host side: those two kernels stay twins (one argument list would change the MSE kernel's
+// code); their entry points are argument checks around one body, composite_train.
 #include <cmath>
 
 #include "common.hpp"
@@ -647,43 +649,6 @@ int nr_composite_bwd(const float* rgb, const float* sigma, const float* z, const
     return NR_OK;
 }
 
-int nr_composite_mse(const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise,
-                     const float* target, int B, int S, int white, float scale, float* rgb_map, float* depth,
-                     float* acc, float* weights, float* loss, float* g_rgb, float* g_sigma, float* g_rd,
-                     unsigned* ticket, void* workspace, nr_stream_t stream) {
-    NR_REQUIRE(rgb && sigma && z && rd && target && rgb_map && loss && g_rgb && g_sigma && workspace && B > 0 && S > 0,
-               "nr_composite_mse: bad arguments");
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    float* sqerr = static_cast<float*>(workspace);
-    const float inv = 1.0f / static_cast<float>(3 * B);
-    const CompositeForm f = composite_form(B, S);
-    // the in-launch loss sum pays up to ~256 workgroups; beyond, the agent-scope release and
-    // ticket of every workgroup cost more than a second one-block launch (measured: 1024
-    // workgroups, 4096 rays, 61 vs 26 + 5 us)
-    if (ticket && ceil_div(B, 4) > 256) ticket = nullptr;
-    if (f.wave) {
-        hipLaunchKernelGGL(composite_mse_wave_kernel, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, target, B, S,
-                           f.K, white, inv, scale, rgb_map, depth, acc, weights, sqerr, g_rgb, g_sigma, g_rd, ticket,
-                           loss);
-        NR_LAUNCH_CHECK("nr_composite_mse");
-        if (!ticket) {
-            hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, s, sqerr, B, inv, loss);
-            NR_LAUNCH_CHECK("nr_composite_mse (loss)");
-        }
-        return NR_OK;
-    }
-    // long rays: the three separate passes (the seed gradient lives in the workspace)
-    float* g_map = sqerr + B;
-    int rc = nr_composite_fwd(rgb, sigma, z, rd, noise, B, S, white, rgb_map, depth, acc, weights, stream);
-    if (rc) return rc;
-    rc = nr_mse_fwd_bwd(rgb_map, target, B, scale, loss, g_map, stream);
-    if (rc) return rc;
-    return nr_composite_bwd(rgb, sigma, z, rd, noise, B, S, white, g_map, nullptr, nullptr, nullptr, g_rgb, g_sigma,
-                            g_rd, stream);
-}
-
-int64_t nr_composite_mse_workspace_bytes(int B) { return B > 0 ? int64_t{16} * B : 0; }
-
 int nr_mse_fwd_bwd(const float* pred, const float* target, int B, float scale, float* loss, float* g,
                    nr_stream_t stream) {
     NR_REQUIRE(pred && target && B > 0, "nr_mse_fwd_bwd: bad arguments");
@@ -721,6 +686,65 @@ int nr_robust_fwd_bwd(const float* pred, const float* target, int B, int kind, f
     return NR_OK;
 }
 
+// The fused training launch.  rho_ray NULL: the MSE form (one loss word, kind and c unused);
+// otherwise the loss family's (two loss words).  sqerr: B floats, then the long-ray seed's 3B.
+static int composite_train(const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise,
+                           const float* target, int B, int S, int white, int kind, float c, float scale,
+                           float* rgb_map, float* depth, float* acc, float* weights, float* loss, float* g_rgb,
+                           float* g_sigma, float* g_rd, unsigned* ticket, float* rho_ray, float* sqerr,
+                           nr_stream_t stream) {
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const float inv = 1.0f / static_cast<float>(3 * B);
+    const CompositeForm f = composite_form(B, S);
+    // the in-launch loss sum pays up to ~256 workgroups; beyond, the agent-scope release and
+    // ticket of every workgroup cost more than a second one-block launch (measured: 1024
+    // workgroups, 4096 rays, 61 vs 26 + 5 us)
+    if (ticket && ceil_div(B, 4) > 256) ticket = nullptr;
+    if (f.wave) {
+#define NR_LAUNCH_ROBUST(KIND)                                                                                     \
+    hipLaunchKernelGGL(composite_robust_wave_kernel<KIND>, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, target, \
+                       B, S, f.K, white, inv, scale, c, rgb_map, depth, acc, weights, sqerr, rho_ray, g_rgb,       \
+                       g_sigma, g_rd, ticket, loss)
+        if (rho_ray) {
+            NR_LOSS_DISPATCH(kind, NR_LAUNCH_ROBUST)
+        } else {
+            hipLaunchKernelGGL(composite_mse_wave_kernel, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, target, B,
+                               S, f.K, white, inv, scale, rgb_map, depth, acc, weights, sqerr, g_rgb, g_sigma, g_rd,
+                               ticket, loss);
+        }
+#undef NR_LAUNCH_ROBUST
+        NR_LAUNCH_CHECK(rho_ray ? "nr_composite_robust" : "nr_composite_mse");
+        if (!ticket) {
+            if (rho_ray) hipLaunchKernelGGL(loss2_sum_kernel, dim3(1), dim3(1024), 0, s, rho_ray, sqerr, B, inv, loss);
+            else hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, s, sqerr, B, inv, loss);
+            NR_LAUNCH_CHECK(rho_ray ? "nr_composite_robust (loss)" : "nr_composite_mse (loss)");
+        }
+        return NR_OK;
+    }
+    // long rays: the three separate passes (the seed gradient lives in the workspace)
+    float* g_map = sqerr + B;
+    int rc = nr_composite_fwd(rgb, sigma, z, rd, noise, B, S, white, rgb_map, depth, acc, weights, stream);
+    if (rc) return rc;
+    rc = rho_ray ? nr_robust_fwd_bwd(rgb_map, target, B, kind, c, scale, loss, g_map, stream)
+                 : nr_mse_fwd_bwd(rgb_map, target, B, scale, loss, g_map, stream);
+    if (rc) return rc;
+    return nr_composite_bwd(rgb, sigma, z, rd, noise, B, S, white, g_map, nullptr, nullptr, nullptr, g_rgb, g_sigma,
+                            g_rd, stream);
+}
+
+int64_t nr_composite_mse_workspace_bytes(int B) { return B > 0 ? int64_t{16} * B : 0; }
+
+int nr_composite_mse(const float* rgb, const float* sigma, const float* z, const float* rd, const float* noise,
+                     const float* target, int B, int S, int white, float scale, float* rgb_map, float* depth,
+                     float* acc, float* weights, float* loss, float* g_rgb, float* g_sigma, float* g_rd,
+                     unsigned* ticket, void* workspace, nr_stream_t stream) {
+    NR_REQUIRE(rgb && sigma && z && rd && target && rgb_map && loss && g_rgb && g_sigma && workspace && B > 0 && S > 0,
+               "nr_composite_mse: bad arguments");
+    return composite_train(rgb, sigma, z, rd, noise, target, B, S, white, NR_LOSS_MSE, 0.f, scale, rgb_map, depth, acc,
+                           weights, loss, g_rgb, g_sigma, g_rd, ticket, nullptr, static_cast<float*>(workspace),
+                           stream);
+}
+
 // workspace: rho per ray (B), squared error per ray (B), the long-ray seed gradient (3B)
 int64_t nr_composite_robust_workspace_bytes(int B) { return B > 0 ? int64_t{20} * B : 0; }
 
@@ -732,34 +756,9 @@ int nr_composite_robust(const float* rgb, const float* sigma, const float* z, co
                "nr_composite_robust: bad arguments");
     NR_REQUIRE(loss_args_ok(kind, c), "nr_composite_robust: kind %d outside NR_LOSS_*, or c = %g not finite and > 0",
                kind, static_cast<double>(c));
-    const hipStream_t s = static_cast<hipStream_t>(stream);
     float* rho_ray = static_cast<float*>(workspace);
-    float* sqerr = rho_ray + B;
-    const float inv = 1.0f / static_cast<float>(3 * B);
-    const CompositeForm f = composite_form(B, S);
-    if (ticket && ceil_div(B, 4) > 256) ticket = nullptr;  // as nr_composite_mse
-    if (f.wave) {
-#define NR_LAUNCH_ROBUST(KIND)                                                                                     \
-    hipLaunchKernelGGL(composite_robust_wave_kernel<KIND>, f.grid, f.block, 0, s, rgb, sigma, z, rd, noise, target, \
-                       B, S, f.K, white, inv, scale, c, rgb_map, depth, acc, weights, sqerr, rho_ray, g_rgb,       \
-                       g_sigma, g_rd, ticket, loss2)
-        NR_LOSS_DISPATCH(kind, NR_LAUNCH_ROBUST)
-#undef NR_LAUNCH_ROBUST
-        NR_LAUNCH_CHECK("nr_composite_robust");
-        if (!ticket) {
-            hipLaunchKernelGGL(loss2_sum_kernel, dim3(1), dim3(1024), 0, s, rho_ray, sqerr, B, inv, loss2);
-            NR_LAUNCH_CHECK("nr_composite_robust (loss)");
-        }
-        return NR_OK;
-    }
-    // long rays: the three separate passes (the seed gradient lives in the workspace)
-    float* g_map = sqerr + B;
-    int rc = nr_composite_fwd(rgb, sigma, z, rd, noise, B, S, white, rgb_map, depth, acc, weights, stream);
-    if (rc) return rc;
-    rc = nr_robust_fwd_bwd(rgb_map, target, B, kind, c, scale, loss2, g_map, stream);
-    if (rc) return rc;
-    return nr_composite_bwd(rgb, sigma, z, rd, noise, B, S, white, g_map, nullptr, nullptr, nullptr, g_rgb, g_sigma,
-                            g_rd, stream);
+    return composite_train(rgb, sigma, z, rd, noise, target, B, S, white, kind, c, scale, rgb_map, depth, acc, weights,
+                           loss2, g_rgb, g_sigma, g_rd, ticket, rho_ray, rho_ray + B, stream);
 }
 
 }  // extern "C"

@@ -209,19 +209,6 @@ def _finish_and_adopt(reducer: GradAllReducer, nets, flats) -> None:
             _adopt_reduced_grad(net, flats)
 
 
-def _loss_and_metrics(out):
-    """(loss_coarse [+ loss_fine], their detached values) of ``render_rays``' output."""
-    loss = out["loss_coarse"]
-    metrics = {"loss_coarse": loss.detach()}  # metrics hold no autograd graph
-    if "loss_fine" in out:
-        loss = loss + out["loss_fine"]
-        metrics["loss_fine"] = out["loss_fine"].detach()
-    for k in ("mse_coarse", "mse_fine"):  # a robust photometric loss: the plain MSE beside it
-        if k in out:
-            metrics[k] = out[k]
-    return loss, metrics
-
-
 def _check_distortion_weight(w) -> float:
     w = float(w)
     if not w >= 0.0:
@@ -249,6 +236,26 @@ def _distortion_term(aux, render_config, weight: float, prescale: float):
     which = "fine" if "weights_fine" in aux else "coarse"
     return ops.distortion_loss(aux["weights_" + which], aux["z_" + which], render_config.near, render_config.far,
                                grad_scale=weight * prescale)
+
+
+def _step_losses(out, aux=None, render_config=None, weight: float = 0.0, prescale: float = 1.0):
+    """(backward sum, logged loss, metrics) of ``render_rays``' output and aux: the sum is
+    loss_coarse [+ loss_fine], plus with ``weight`` > 0 the distortion term, which the
+    logged loss counts ``weight`` times and ``metrics["loss_distortion"]`` holds unweighted."""
+    bwd = loss = out["loss_coarse"]
+    metrics = {"loss_coarse": loss.detach()}  # metrics hold no autograd graph
+    if "loss_fine" in out:
+        bwd = loss = loss + out["loss_fine"]
+        metrics["loss_fine"] = out["loss_fine"].detach()
+    for k in ("mse_coarse", "mse_fine"):  # a robust photometric loss: the plain MSE beside it
+        if k in out:
+            metrics[k] = out[k]
+    if weight > 0:
+        dist = _distortion_term(aux, render_config, weight, prescale)
+        metrics["loss_distortion"] = dist.detach()
+        loss = loss.detach() + weight * dist.detach()
+        bwd = bwd + dist
+    return bwd, loss, metrics
 
 
 class Trainer:
@@ -324,21 +331,18 @@ class Trainer:
 
         # the MSE losses (train.py:89/98) come out of the compositing (ops.composite_mse)
         dw = self.distortion_weight
-        out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
-                          t_rand=t_rand, u=u, return_aux=dw > 0, coarse_stream=cs,
-                          coarse_backward=coarse_backward if cs is not None else None,
-                          target_rgb=target_rgb, loss_scale=gs, photometric=self.photometric)
-        dist = None
-        if dw > 0:
-            out, aux = out
-            dist = _distortion_term(aux, self.render_config, dw, gs)
+        out, aux = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
+                               t_rand=t_rand, u=u, return_aux=True, coarse_stream=cs,
+                               coarse_backward=coarse_backward if cs is not None else None,
+                               target_rgb=target_rgb, loss_scale=gs, photometric=self.photometric)
         if cs is not None:
             main = torch.cuda.current_stream(rays_o.device)
             loss_f = out["loss_fine"]
             loss_c = early["loss_c"].detach()
             lf = loss_f.detach()
             term = None
-            if dist is not None:  # the fine chain's: on the main stream, before its backward
+            if dw > 0:  # the fine chain's: on the main stream, before its backward
+                dist = _distortion_term(aux, self.render_config, dw, gs)
                 loss_f = loss_f + dist
                 term = dw * dist.detach()
             fine_done = main.record_event()
@@ -359,15 +363,11 @@ class Trainer:
             metrics = {"loss_coarse": loss_c, "loss_fine": lf}
             if "mse_c" in early:
                 metrics["mse_coarse"], metrics["mse_fine"] = early["mse_c"], out["mse_fine"]
+            if dw > 0:
+                metrics["loss_distortion"] = dist.detach()
         else:
-            loss, metrics = _loss_and_metrics(out)
-            if dist is None:
-                loss.backward(ops.unit_grad(loss.device))
-            else:
-                (loss + dist).backward(ops.unit_grad(loss.device))
-                loss = loss.detach() + dw * dist.detach()
-        if dist is not None:
-            metrics["loss_distortion"] = dist.detach()
+            bwd, loss, metrics = _step_losses(out, aux, self.render_config, dw, gs)
+            bwd.backward(ops.unit_grad(loss.device))
         if self.reducer is not None:
             _finish_and_adopt(self.reducer, (self.model_coarse, self.model_fine),
                               [flat for _, flat in self.reducer.pending])
@@ -474,18 +474,10 @@ class PoseTrainer:
         gs = self.reducer.prescale if self.reducer is not None else 1.0  # DP: 1/world in the seed
         # the MSE losses (train_pose_opt.py:355-370) come out of the compositing
         dw = self.distortion_weight
-        out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
-                          t_rand=t_rand, u=u, return_aux=dw > 0, target_rgb=target, loss_scale=gs,
-                          photometric=self.photometric)
-        if dw > 0:
-            out, aux = out
-        loss, metrics = _loss_and_metrics(out)
-        bwd = loss
-        if dw > 0:
-            dist = _distortion_term(aux, self.render_config, dw, gs)
-            metrics["loss_distortion"] = dist.detach()
-            loss = loss + dw * dist.detach()
-            bwd = bwd + dist
+        out, aux = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
+                               t_rand=t_rand, u=u, return_aux=True, target_rgb=target, loss_scale=gs,
+                               photometric=self.photometric)
+        bwd, loss, metrics = _step_losses(out, aux, self.render_config, dw, gs)
         if optimize_poses:
             # the regulariser is replicated on every rank: its gradient carries the seed's
             # 1/world too, so the SUM over the ranks counts it once
@@ -581,8 +573,8 @@ class PoseRefiner:
         out = render_rays(self.model_coarse, self.model_fine, rays_o, rays_d, self.render_config, is_train=True,
                           t_rand=t_rand, u=u, target_rgb=pixel_batch.target_rgb,
                           photometric=self.photometric)
-        loss, metrics = _loss_and_metrics(out)
-        loss.backward(ops.unit_grad(loss.device))
+        bwd, loss, metrics = _step_losses(out)
+        bwd.backward(ops.unit_grad(loss.device))
         self.optimizer_poses.step(clip_groups=[(self.poses, self.max_norm)])
         if self.scheduler_poses is not None:
             self.scheduler_poses.step()

@@ -362,93 +362,17 @@ def composite(rgb, sigma, z_vals, rays_d, noise=None, white_background=True):
     return _Composite.apply(rgb, sig, z_vals, rays_d, noise, bool(white_background))
 
 
-class _CompositeMSE(torch.autograd.Function):
-    """raw2outputs + mean((rgb_map - target)^2) of one training step, one launch pair
-    (nr_composite_mse): the forward also produces the gradient of ``grad_scale * loss``
-    w.r.t. rgb / sigma (/ rays_d), which the backward hands over (bit-identical to the
-    composite forward, MSE and composite backward run separately).  Gradients arriving
-    at rgb_map / depth / acc / weights from elsewhere add a composite backward of their own."""
-
-    @staticmethod
-    def forward(ctx, rgb, sigma, z, rays_d, noise, target, white, grad_scale, ticket):
-        rgb, sigma, z, rd, tgt = _c(rgb), _c(sigma), _c(z), _c(rays_d), _c(target)
-        B, S = z.shape
-        nz = _c(noise)
-        dev = z.device
-        rgb_map = torch.empty(B, 3, device=dev, dtype=_f32)
-        depth = torch.empty(B, device=dev, dtype=_f32)
-        acc = torch.empty(B, device=dev, dtype=_f32)
-        weights = torch.empty(B, S, device=dev, dtype=_f32)
-        loss = torch.empty((), device=dev, dtype=_f32)
-        g_rgb = torch.empty_like(rgb)
-        g_sigma = torch.empty(B, S, device=dev, dtype=_f32)
-        g_rd = torch.zeros_like(rd) if ctx.needs_input_grad[3] else None
-        ws = torch.empty(max(16, int(_hip.load().nr_composite_mse_workspace_bytes(B))), device=dev, dtype=torch.uint8)
-        call("nr_composite_mse", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), ptr(tgt), B, S, int(white),
-             float(grad_scale), ptr(rgb_map), ptr(depth), ptr(acc), ptr(weights), ptr(loss), ptr(g_rgb), ptr(g_sigma),
-             ptr(g_rd), ptr(ticket), ptr(ws), _stream())
-        ctx.save_for_backward(rgb, sigma, z, rd, nz, g_rgb, g_sigma, g_rd)
-        ctx.white = white
-        ctx.sigma_shape = sigma.shape
-        ctx.set_materialize_grads(False)
-        return loss, rgb_map, depth, acc, weights
-
-    @staticmethod
-    def backward(ctx, g_loss, g_map, g_depth, g_acc, g_w):
-        g_rgb, g_sigma, g_rd = _composite_loss_backward(ctx, g_loss, g_map, g_depth, g_acc, g_w)
-        return g_rgb, g_sigma, None, g_rd, None, None, None, None, None
-
-
-def _composite_loss_backward(ctx, g_loss, g_map, g_depth, g_acc, g_w):
-    """The backward of the fused compositing, whichever photometric loss seeded it: the
-    stored gradient of the loss times ``g_loss``, plus a composite backward of their own
-    for gradients arriving at the other outputs."""
-    rgb, sigma, z, rd, nz, g_rgb, g_sigma, g_rd = ctx.saved_tensors
-    B, S = z.shape
-    if g_loss is None:
-        g_rgb, g_sigma = torch.zeros_like(g_rgb), torch.zeros_like(g_sigma)
-        g_rd = torch.zeros_like(g_rd) if g_rd is not None else None
-    elif g_loss.data_ptr() != _unit.get(g_loss.device, _NO_UNIT).data_ptr():
-        g_rgb, g_sigma = g_rgb * g_loss, g_sigma * g_loss
-        g_rd = g_rd * g_loss if g_rd is not None else None
-    if any(t is not None for t in (g_map, g_depth, g_acc, g_w)):
-        e_rgb, e_sigma = torch.empty_like(rgb), torch.empty(B, S, device=z.device, dtype=_f32)
-        e_rd = torch.zeros_like(rd) if g_rd is not None else None
-        gm = _c(g_map) if g_map is not None else torch.zeros(B, 3, device=z.device, dtype=_f32)
-        call("nr_composite_bwd", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), B, S, int(ctx.white), ptr(gm),
-             ptr(_c(g_depth)), ptr(_c(g_acc)), ptr(_c(g_w)), ptr(e_rgb), ptr(e_sigma), ptr(e_rd), _stream())
-        g_rgb, g_sigma = g_rgb + e_rgb, g_sigma + e_sigma
-        g_rd = g_rd + e_rd if g_rd is not None else None
-    return g_rgb, g_sigma.view(ctx.sigma_shape), g_rd
-
-
-def composite_mse(rgb, sigma, z_vals, rays_d, target, noise=None, white_background=True, grad_scale=1.0,
-                  ticket=None):
-    """Training form of raw2outputs + the MSE loss against ``target`` (B,3): returns
-    (loss, rgb_map, depth, acc, weights); the loss's gradient carries ``grad_scale``.
-    ``ticket``: a persistent zeroed int32 device word (NeRF.loss_ticket) that lets the
-    launch sum the loss itself; calls sharing it must not run concurrently."""
-    _check(rgb, sigma, z_vals, rays_d, target, noise, ticket)
-    sig = sigma.reshape(z_vals.shape)
-    return _CompositeMSE.apply(rgb, sig, z_vals, rays_d, noise, target, bool(white_background), float(grad_scale),
-                               ticket)
-
-
-# The photometric loss family, in the order of the header's NR_LOSS_* enum.
-LOSS_KINDS = ("mse", "huber", "charbonnier", "cauchy", "geman_mcclure")
-
-
-def loss_kind_index(kind: str) -> int:
-    if kind not in LOSS_KINDS:
-        raise ValueError(f"loss kind must be one of {', '.join(LOSS_KINDS)}, got {kind!r}")
-    return LOSS_KINDS.index(kind)
-
-
 class _CompositeLoss(torch.autograd.Function):
-    """_CompositeMSE with a member of the robust loss family in the seed
-    (nr_composite_robust): outputs (loss, mse, rgb_map, depth, acc, weights), where
-    ``loss`` is the mean of rho and ``mse`` the plain mean squared error of the same
-    rgb_map, not differentiable."""
+    """raw2outputs + the photometric loss of one training step, one launch pair: the forward
+    also produces the gradient of ``grad_scale * loss`` w.r.t. rgb / sigma (/ rays_d), which
+    the backward hands over (bit-identical to the composite forward, the loss seed and the
+    composite backward run separately).  Gradients arriving at rgb_map / depth / acc /
+    weights from elsewhere add a composite backward of their own.
+    ``kind`` None: the plain MSE, mean((rgb_map - target)^2) (nr_composite_mse), outputs
+    (loss, rgb_map, depth, acc, weights).  An index of LOSS_KINDS: that member of the robust
+    family at scale ``c`` (nr_composite_robust), outputs (loss, mse, ...) where ``loss`` is
+    the mean of rho and ``mse`` the plain mean squared error of the same rgb_map, not
+    differentiable.  Which of the two only picks the entry point and its loss words."""
 
     @staticmethod
     def forward(ctx, rgb, sigma, z, rays_d, noise, target, white, grad_scale, ticket, kind, c):
@@ -460,27 +384,67 @@ class _CompositeLoss(torch.autograd.Function):
         depth = torch.empty(B, device=dev, dtype=_f32)
         acc = torch.empty(B, device=dev, dtype=_f32)
         weights = torch.empty(B, S, device=dev, dtype=_f32)
-        loss2 = torch.empty(2, device=dev, dtype=_f32)
+        loss = torch.empty(() if kind is None else 2, device=dev, dtype=_f32)
         g_rgb = torch.empty_like(rgb)
         g_sigma = torch.empty(B, S, device=dev, dtype=_f32)
         g_rd = torch.zeros_like(rd) if ctx.needs_input_grad[3] else None
-        ws = torch.empty(max(16, int(_hip.load().nr_composite_robust_workspace_bytes(B))), device=dev,
+        entry, family = ("nr_composite_mse", ()) if kind is None else ("nr_composite_robust", (int(kind), float(c)))
+        ws = torch.empty(max(16, int(getattr(_hip.load(), entry + "_workspace_bytes")(B))), device=dev,
                          dtype=torch.uint8)
-        call("nr_composite_robust", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), ptr(tgt), B, S, int(white),
-             int(kind), float(c), float(grad_scale), ptr(rgb_map), ptr(depth), ptr(acc), ptr(weights), ptr(loss2),
-             ptr(g_rgb), ptr(g_sigma), ptr(g_rd), ptr(ticket), ptr(ws), _stream())
+        call(entry, ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), ptr(tgt), B, S, int(white), *family,
+             float(grad_scale), ptr(rgb_map), ptr(depth), ptr(acc), ptr(weights), ptr(loss), ptr(g_rgb), ptr(g_sigma),
+             ptr(g_rd), ptr(ticket), ptr(ws), _stream())
         ctx.save_for_backward(rgb, sigma, z, rd, nz, g_rgb, g_sigma, g_rd)
         ctx.white = white
         ctx.sigma_shape = sigma.shape
         ctx.set_materialize_grads(False)
-        loss, mse = loss2[0], loss2[1]
+        if kind is None:
+            return loss, rgb_map, depth, acc, weights
+        loss, mse = loss[0], loss[1]
         ctx.mark_non_differentiable(mse)
         return loss, mse, rgb_map, depth, acc, weights
 
     @staticmethod
-    def backward(ctx, g_loss, g_mse, g_map, g_depth, g_acc, g_w):
-        g_rgb, g_sigma, g_rd = _composite_loss_backward(ctx, g_loss, g_map, g_depth, g_acc, g_w)
-        return g_rgb, g_sigma, None, g_rd, None, None, None, None, None, None, None
+    def backward(ctx, g_loss, *g_outs):
+        g_map, g_depth, g_acc, g_w = g_outs[-4:]  # after the loss, and the mse of the robust form
+        rgb, sigma, z, rd, nz, g_rgb, g_sigma, g_rd = ctx.saved_tensors
+        B, S = z.shape
+        if g_loss is None:
+            g_rgb, g_sigma = torch.zeros_like(g_rgb), torch.zeros_like(g_sigma)
+            g_rd = torch.zeros_like(g_rd) if g_rd is not None else None
+        else:
+            g_rgb, g_sigma, g_rd = _seeded(g_loss, g_rgb, g_sigma, g_rd)
+        if any(t is not None for t in (g_map, g_depth, g_acc, g_w)):
+            e_rgb, e_sigma = torch.empty_like(rgb), torch.empty(B, S, device=z.device, dtype=_f32)
+            e_rd = torch.zeros_like(rd) if g_rd is not None else None
+            gm = _c(g_map) if g_map is not None else torch.zeros(B, 3, device=z.device, dtype=_f32)
+            call("nr_composite_bwd", ptr(rgb), ptr(sigma), ptr(z), ptr(rd), ptr(nz), B, S, int(ctx.white), ptr(gm),
+                 ptr(_c(g_depth)), ptr(_c(g_acc)), ptr(_c(g_w)), ptr(e_rgb), ptr(e_sigma), ptr(e_rd), _stream())
+            g_rgb, g_sigma = g_rgb + e_rgb, g_sigma + e_sigma
+            g_rd = g_rd + e_rd if g_rd is not None else None
+        return g_rgb, g_sigma.view(ctx.sigma_shape), None, g_rd, None, None, None, None, None, None, None
+
+
+def composite_mse(rgb, sigma, z_vals, rays_d, target, noise=None, white_background=True, grad_scale=1.0,
+                  ticket=None):
+    """Training form of raw2outputs + the MSE loss against ``target`` (B,3): returns
+    (loss, rgb_map, depth, acc, weights); the loss's gradient carries ``grad_scale``.
+    ``ticket``: a persistent zeroed int32 device word (NeRF.loss_ticket) that lets the
+    launch sum the loss itself; calls sharing it must not run concurrently."""
+    _check(rgb, sigma, z_vals, rays_d, target, noise, ticket)
+    sig = sigma.reshape(z_vals.shape)
+    return _CompositeLoss.apply(rgb, sig, z_vals, rays_d, noise, target, bool(white_background), float(grad_scale),
+                                ticket, None, 0.0)
+
+
+# The photometric loss family, in the order of the header's NR_LOSS_* enum.
+LOSS_KINDS = ("mse", "huber", "charbonnier", "cauchy", "geman_mcclure")
+
+
+def loss_kind_index(kind: str) -> int:
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"loss kind must be one of {', '.join(LOSS_KINDS)}, got {kind!r}")
+    return LOSS_KINDS.index(kind)
 
 
 def composite_loss(rgb, sigma, z_vals, rays_d, target, kind, c, noise=None, white_background=True, grad_scale=1.0,
@@ -673,35 +637,15 @@ def adam_multi(spans, lr, beta1, beta2, eps, step, sched: Optional[torch.Tensor]
          _stream())
 
 
-class _MSE(torch.autograd.Function):
-    """mean((pred - target)^2) (train.py:89); the gradient is produced in the same kernel,
-    times ``grad_scale`` (data parallelism folds its 1/world into it: the all-reduced
-    SUM of the ranks' gradients is then the global-batch mean with no extra launch)."""
-
-    @staticmethod
-    def forward(ctx, pred, target, grad_scale):
-        loss, g = mse_loss_and_grad(pred, target, grad_scale)
-        ctx.save_for_backward(g)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        (g,) = ctx.saved_tensors
-        # seeded by unit_grad(): gl is exactly 1.0, so g * gl == g (no multiply launch)
-        if gl.data_ptr() == _unit.get(gl.device, _NO_UNIT).data_ptr():
-            return g, None, None
-        return g * gl, None, None
-
-
 _unit = {}
 _NO_UNIT = torch.empty(0)
 
 
 def unit_grad(device) -> torch.Tensor:
     """A cached device scalar 1.0 to seed ``loss.backward(unit_grad(dev))``: no fill
-    kernel for the seed, and the MSE backward (reached through sums of losses, whose
-    backward forwards the seed tensor itself) skips its multiply by it.  Never write
-    into it."""
+    kernel for the seed, and the loss backwards (reached through sums of losses, whose
+    backward forwards the seed tensor itself) skip their multiply by it (``_seeded``).
+    Never write into it."""
     u = _unit.get(device)
     if u is None:
         u = torch.ones((), device=device, dtype=_f32)
@@ -709,10 +653,13 @@ def unit_grad(device) -> torch.Tensor:
     return u
 
 
-def mse_loss(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) -> torch.Tensor:
-    """The loss value is always the plain mean; only its gradient carries ``grad_scale``."""
-    _check(pred, target)
-    return _MSE.apply(pred, target, float(grad_scale))
+def _seeded(g_loss, *grads):
+    """The stored gradients ``grads`` of a loss (None stays None) times the gradient
+    ``g_loss`` arriving at it.  Seeded by ``unit_grad()``, ``g_loss`` is exactly 1.0 and
+    these are the stored tensors themselves (no multiply launch); otherwise one multiply each."""
+    if g_loss.data_ptr() == _unit.get(g_loss.device, _NO_UNIT).data_ptr():
+        return grads
+    return tuple(g * g_loss if g is not None else None for g in grads)
 
 
 def robust_loss_and_grad(pred, target, kind, c, scale=1.0):
@@ -727,28 +674,39 @@ def robust_loss_and_grad(pred, target, kind, c, scale=1.0):
     return loss2, g
 
 
-class _Robust(torch.autograd.Function):
-    """_MSE for the robust loss family: the mean of rho(pred - target)."""
+class _PhotometricLoss(torch.autograd.Function):
+    """The stand-alone loss seed: mean((pred - target)^2) (train.py:89) for ``kind`` None,
+    the mean of rho(pred - target) of that LOSS_KINDS name at scale ``c`` otherwise (which
+    of the two only picks the entry point).  The gradient is produced in the same kernel,
+    times ``grad_scale`` (data parallelism folds its 1/world into it: the all-reduced SUM
+    of the ranks' gradients is then the global-batch mean with no extra launch)."""
 
     @staticmethod
-    def forward(ctx, pred, target, kind, c, grad_scale):
-        loss2, g = robust_loss_and_grad(pred, target, kind, c, grad_scale)
+    def forward(ctx, pred, target, grad_scale, kind, c):
+        if kind is None:
+            loss, g = mse_loss_and_grad(pred, target, grad_scale)
+        else:
+            loss2, g = robust_loss_and_grad(pred, target, kind, c, grad_scale)
+            loss = loss2[0]
         ctx.save_for_backward(g)
-        return loss2[0]
+        return loss
 
     @staticmethod
     def backward(ctx, gl):
-        (g,) = ctx.saved_tensors
-        if gl.data_ptr() == _unit.get(gl.device, _NO_UNIT).data_ptr():
-            return g, None, None, None, None
-        return g * gl, None, None, None, None
+        return _seeded(gl, *ctx.saved_tensors)[0], None, None, None, None
+
+
+def mse_loss(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) -> torch.Tensor:
+    """The loss value is always the plain mean; only its gradient carries ``grad_scale``."""
+    _check(pred, target)
+    return _PhotometricLoss.apply(pred, target, float(grad_scale), None, 0.0)
 
 
 def robust_loss(pred: torch.Tensor, target: torch.Tensor, kind: str, c: float, scale: float = 1.0) -> torch.Tensor:
     """``mse_loss`` with the photometric loss ``kind`` (one of LOSS_KINDS) at scale ``c``; the
     value is the plain mean of rho, only its gradient carries ``scale``."""
     _check(pred, target)
-    return _Robust.apply(pred, target, kind, float(c), float(scale))
+    return _PhotometricLoss.apply(pred, target, float(scale), kind, float(c))
 
 
 class _Distortion(torch.autograd.Function):
@@ -775,10 +733,7 @@ class _Distortion(torch.autograd.Function):
         (g,) = ctx.saved_tensors
         if g is None:
             return None, None, None, None, None
-        # seeded by unit_grad(): gl is exactly 1.0 (no multiply launch), as in _MSE
-        if gl.data_ptr() != _unit.get(gl.device, _NO_UNIT).data_ptr():
-            g = g * gl
-        return g.view(ctx.w_shape), None, None, None, None
+        return _seeded(gl, g)[0].view(ctx.w_shape), None, None, None, None
 
 
 def distortion_loss(weights: torch.Tensor, z_vals: torch.Tensor, near: float, far: float,

@@ -54,19 +54,13 @@ def _outputs(rgb, sigma, z_vals, rays_d, raw_noise_std, white_background, target
     if raw_noise_std > 0.0:
         noise = torch.randn(*z_vals.shape[:-1], S, device=z_vals.device) * raw_noise_std
     ticket = net.loss_ticket(z_vals.device) if hasattr(net, "loss_ticket") else None
+    fused, family, keys = ops.composite_mse, (), ("loss",)
     if photometric is not None and photometric[0] != "mse":
-        loss, mse, rgb_map, depth, acc, weights = ops.composite_loss(
-            rgb.reshape(-1, S, 3), sigma.reshape(-1, S), z_vals.reshape(-1, S), rays_d.reshape(-1, 3), target_rgb,
-            photometric[0], photometric[1], noise=None if noise is None else noise.reshape(-1, S),
-            white_background=white_background, grad_scale=loss_scale, ticket=ticket)
-        return {"rgb_map": rgb_map, "depth_map": depth, "acc_map": acc, "weights": weights, "loss": loss,
-                "mse": mse}
-    loss, rgb_map, depth, acc, weights = ops.composite_mse(
-        rgb.reshape(-1, S, 3), sigma.reshape(-1, S), z_vals.reshape(-1, S), rays_d.reshape(-1, 3), target_rgb,
-        noise=None if noise is None else noise.reshape(-1, S), white_background=white_background,
-        grad_scale=loss_scale,
-        ticket=ticket)
-    return {"rgb_map": rgb_map, "depth_map": depth, "acc_map": acc, "weights": weights, "loss": loss}
+        fused, family, keys = ops.composite_loss, photometric, ("loss", "mse")
+    out = fused(rgb.reshape(-1, S, 3), sigma.reshape(-1, S), z_vals.reshape(-1, S), rays_d.reshape(-1, 3), target_rgb,
+                *family, noise=None if noise is None else noise.reshape(-1, S), white_background=white_background,
+                grad_scale=loss_scale, ticket=ticket)
+    return dict(zip(keys + ("rgb_map", "depth_map", "acc_map", "weights"), out))
 
 
 def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Tensor, rays_d: torch.Tensor,
@@ -106,7 +100,26 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
     # the view directions per sample (rendering.py:165) come out of the sampling launch
     pts, z_c, vd = ops.stratified_sample(rays_o, rays_d, config.near, config.far, Nc,
                                          t_rand=t_rand if perturb else None, viewdirs=True)
-    if coarse_stream is not None:
+    results, aux = {}, {}
+
+    def render(model, pts, vd, z, name):
+        """One network's forward and compositing over the samples ``z``, on the current
+        stream; its maps, losses and aux entries go in under ``name``."""
+        S = z.shape[-1]
+        rgb, sigma = model(pts.reshape(-1, 3), vd)
+        out = _outputs(rgb.reshape(N_rays, S, 3), sigma.reshape(N_rays, S, 1), z, rays_d, raw_noise_std,
+                       config.white_background, target_rgb, loss_scale, model, photometric)
+        for k in ("rgb", "depth", "acc"):
+            results[f"{k}_{name}"] = out[k + "_map"]
+        for k in ("loss", "mse"):
+            if k in out:
+                results[f"{k}_{name}"] = out[k]
+        aux["z_" + name], aux["weights_" + name] = z, out["weights"]
+        return out
+
+    if coarse_stream is None:
+        out_c = render(model_coarse, pts, vd, z_c, "coarse")
+    else:
         main = torch.cuda.current_stream(rays_o.device)
         coarse_stream.wait_stream(main)
         # these blocks come from the current stream's pool and the coarse chain (its
@@ -116,10 +129,7 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
         for t in (pts, vd, z_c, rays_d) + ((target_rgb,) if target_rgb is not None else ()):
             t.record_stream(coarse_stream)
         with torch.cuda.stream(coarse_stream):
-            rgb_c, sigma_c = model_coarse(pts.reshape(-1, 3), vd)
-            out_c = _outputs(rgb_c.reshape(N_rays, Nc, 3), sigma_c.reshape(N_rays, Nc, 1), z_c, rays_d,
-                             raw_noise_std, config.white_background, target_rgb, loss_scale, model_coarse,
-                             photometric)
+            out_c = render(model_coarse, pts, vd, z_c, "coarse")
             if coarse_backward is not None:
                 forward_done = coarse_stream.record_event()
                 coarse_backward(out_c)
@@ -127,21 +137,6 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
             main.wait_event(forward_done)
         else:
             main.wait_stream(coarse_stream)
-    else:
-        rgb_c, sigma_c = model_coarse(pts.reshape(-1, 3), vd)
-        out_c = _outputs(rgb_c.reshape(N_rays, Nc, 3), sigma_c.reshape(N_rays, Nc, 1), z_c, rays_d,
-                         raw_noise_std, config.white_background, target_rgb, loss_scale, model_coarse,
-                         photometric)
-    results = {
-        "rgb_coarse": out_c["rgb_map"],
-        "depth_coarse": out_c["depth_map"],
-        "acc_coarse": out_c["acc_map"],
-    }
-    if "loss" in out_c:
-        results["loss_coarse"] = out_c["loss"]
-    if "mse" in out_c:
-        results["mse_coarse"] = out_c["mse"]
-    aux = {"z_coarse": z_c, "weights_coarse": out_c["weights"]}
     if config.use_hierarchical and model_fine is not None:
         Nf = config.num_samples_fine
         det = not is_train
@@ -149,20 +144,7 @@ def render_rays(model_coarse: NeRF, model_fine: Optional[NeRF], rays_o: torch.Te
             u = torch.rand(N_rays, Nf, device=rays_o.device)
         pts_f, z_f, vd_f = ops.sample_hierarchical(rays_o, rays_d, z_c, out_c["weights"], Nf, u=None if det else u,
                                                    viewdirs=True)
-        T = z_f.shape[-1]
-        rgb_f, sigma_f = model_fine(pts_f.reshape(-1, 3), vd_f)
-        out_f = _outputs(rgb_f.reshape(N_rays, T, 3), sigma_f.reshape(N_rays, T, 1), z_f, rays_d,
-                         raw_noise_std, config.white_background, target_rgb, loss_scale, model_fine,
-                         photometric)
-        if "loss" in out_f:
-            results["loss_fine"] = out_f["loss"]
-        if "mse" in out_f:
-            results["mse_fine"] = out_f["mse"]
-        results["rgb_fine"] = out_f["rgb_map"]
-        results["depth_fine"] = out_f["depth_map"]
-        results["acc_fine"] = out_f["acc_map"]
-        aux["z_fine"] = z_f
-        aux["weights_fine"] = out_f["weights"]
+        render(model_fine, pts_f, vd_f, z_f, "fine")
     if return_aux:
         return results, aux
     return results

@@ -388,6 +388,45 @@ def test_op_chain_matches_the_oracle_with_extra_output_grads(kind, B, S):
     assert _same(a2.grad, a3.grad) and _same(s2.grad, s3.grad)
 
 
+@pytest.mark.parametrize("path", ["composite_mse", "composite_loss_mse", "composite_loss_huber"])
+@pytest.mark.parametrize("B,S", [(5, 65), (3, 600)], ids=["wave_per_ray", "three_pass"])
+def test_fused_backward_is_exact_in_its_seed_and_its_extra_output_grads(B, S, path):
+    """The one backward behind ops.composite_mse and ops.composite_loss, pinned by exact
+    relations (no tolerance): (a) a fresh seed tensor 0.5 gives 0.5 x the gradients of the
+    unit_grad() seed, bit for bit (a power of two: the products are exact); (b) with the
+    loss unused, gradients arriving at rgb_map / depth / weights alone give ops.composite's
+    backward of the same inputs; (c) both in one backward give the elementwise fp32 sum."""
+    from noisy_src import ops
+    dv = {k: (None if v is None else v.to(DEV)) for k, v in ei.composite_inputs(S, B, "random").items()}
+    ups = (dv["g_map"], dv["g_depth"], dv["g_w"])
+
+    def run(fused, seed, with_ups):
+        leaves = [dv[n].clone().requires_grad_(True) for n in ("rgb", "sigma", "rd")]
+        if not fused:
+            out = ops.composite(leaves[0], leaves[1], dv["z"], leaves[2], noise=dv["noise"])
+        elif path == "composite_mse":
+            out = ops.composite_mse(leaves[0], leaves[1], dv["z"], leaves[2], dv["target"], noise=dv["noise"])
+        else:
+            out = ops.composite_loss(leaves[0], leaves[1], dv["z"], leaves[2], dv["target"], path.rsplit("_", 1)[1],
+                                     0.1, noise=dv["noise"])
+        rgb_map, depth, _, w = out[-4:]
+        outs, gos = ([out[0]], [seed]) if seed is not None else ([], [])
+        if with_ups:
+            outs, gos = outs + [rgb_map, depth, w], gos + list(ups)
+        return torch.autograd.grad(outs, leaves, grad_outputs=gos)
+
+    unit = run(True, ops.unit_grad(dv["z"].device), False)
+    assert all(g.abs().max() > 0 for g in unit)
+    half = run(True, torch.full((), 0.5, device=DEV), False)
+    extra = run(True, None, True)
+    both = run(True, ops.unit_grad(dv["z"].device), True)
+    plain = run(False, None, True)
+    for name, u, h, e, b, p in zip(("rgb", "sigma", "rays_d"), unit, half, extra, both, plain):
+        assert torch.equal(h, 0.5 * u), ("a", name)
+        assert torch.equal(e, p), ("b", name)
+        assert torch.equal(b, u + e), ("c", name)
+
+
 # ---------------------------------------------------------------------- 7. trainers --
 C = 0.1
 

@@ -11,11 +11,13 @@ diff the two outputs: a refactor of composite.hip or sampling.hip changes no lin
 
 Cases: nr_composite_fwd (depth / acc / weights present and NULL), nr_composite_bwd (g_depth /
 g_acc / g_w all present and all NULL, g_rays_d present and NULL; its g_map is nr_mse_fwd_bwd's
-gradient of the forward's rgb_map, whose loss word is hashed as well) and nr_composite_mse
+gradient of the forward's rgb_map, whose loss word is hashed as well), nr_composite_mse
 (nullable outputs, g_rays_d and the ticket each present and NULL; the loss word and the ticket
-are hashed) at S = 1 .. 600 (wave per ray up to 512, thread per ray beyond), B = 1, 3, 5 (dead
-waves in the last workgroup) and 700, both backgrounds, the three regimes of edge_inputs;
-nr_composite_mse also at B = 4096, S = 64, where the entry point drops the ticket.
+are hashed) and nr_composite_robust (the five loss kinds at c = 0.1, the ticket present and
+NULL; both loss words and the ticket are hashed) at S = 1 .. 600 (wave per ray up to 512,
+thread per ray beyond), B = 1, 3, 5 (dead waves in the last workgroup) and 700, both
+backgrounds, the three regimes of edge_inputs; nr_composite_mse and nr_composite_robust also
+at B = 4096, S = 64, where the entry points drop the ticket.
 nr_sample_hierarchical at edge_inputs.HIER_SIZES (sample_hier_kernel<1, 2, 4, 8>) and at
 (256, 512) (the long kernel), B = 1 and 5, points, view directions and u each present and NULL.
 Every output buffer starts as NaN; g_rays_d, which is accumulated, starts from the case's
@@ -40,6 +42,7 @@ DEV = "cuda"
 NAN = float("nan")
 BITS_S = (1, 2, 63, 64, 65, 130, 192, 511, 512, 513, 600)
 BITS_B = (1, 3, 5, 700)
+LOSS_KINDS, ROBUST_C = ("mse", "huber", "charbonnier", "cauchy", "geman_mcclure"), 0.1  # the header's NR_LOSS_* order
 LAUNCHES, REPEATS, WARMUP = 200, 5, 50
 
 
@@ -100,6 +103,17 @@ def composite_bits(S, B, white, regime, mse_only=False):
              ptr(o.get("acc")), ptr(o.get("weights")), ptr(o["loss"]), ptr(o["g_rgb"]), ptr(o["g_sigma"]),
              ptr(o.get("g_rays_d")), ptr(o.get("ticket")), ptr(ws), stream)
         emit(f"composite_mse/{case}/outs{int(outs)}/rd{int(with_rd)}/ticket{int(ticket)}", **o)
+    ws_bytes = int(_hip.load().nr_composite_robust_workspace_bytes(B))
+    for (kind, name), ticket in itertools.product(enumerate(LOSS_KINDS), (True, False)):
+        o = dict(rgb_map=nans(B, 3), depth=nans(B), acc=nans(B), weights=nans(B, S), loss2=nans(2), g_rgb=nans(B, S, 3),
+                 g_sigma=nans(B, S), g_rays_d=c["rd_init"].clone())
+        if ticket:
+            o["ticket"] = torch.zeros(4, device=DEV, dtype=torch.int32)
+        ws = nans(ws_bytes // 4)
+        call("nr_composite_robust", *front, ptr(c["target"]), B, S, white, kind, ROBUST_C, scale, ptr(o["rgb_map"]),
+             ptr(o["depth"]), ptr(o["acc"]), ptr(o["weights"]), ptr(o["loss2"]), ptr(o["g_rgb"]), ptr(o["g_sigma"]),
+             ptr(o["g_rays_d"]), ptr(o.get("ticket")), ptr(ws), stream)
+        emit(f"composite_robust/{case}/{name}/ticket{int(ticket)}", **o)
 
 
 def hier_bits():

@@ -15,7 +15,7 @@ The json records the three things the step's cost is made of:
   rendered batch, bracketed by HIP events over CALLS back-to-back launches, against the time
   of moving its own 12 B per sample (read w, read z, write g_w) at bench.PEAK_HBM_GBS.
 * ``extra_composite_bwd``: the ``nr_composite_bwd`` with ``g_weights`` that a non-zero weight adds
-  to the step (``_CompositeMSE.backward``), timed the same way, plus the elementwise sums that
+  to the step (``ops._CompositeLoss.backward``), timed the same way, plus the elementwise sums that
   join its gradients to the fused launch's.
 
 python tools/distortion_ab.py [--parent-bench FILE] [--out FILE] [--steps 200] [--warmup 20]
