@@ -1,6 +1,8 @@
-// Fused NeRF MLP on MFMA (gfx950): the plan and the extern "C" entry points.  Each entry
-// point fills the argument structs of mlp_launch.hpp from the plan and calls the
-// launchers of the translation units that hold the kernels:
+// Fused NeRF MLP on MFMA (gfx950): the plan and the extern "C" entry points.  An entry point
+// is: plan (make_plan refuses a config that has no launch), pointer checks, sizes, the
+// launch's arguments, launch.  The weight streams, the dW and the reduce arguments come from
+// the pure builders beside the plan (mlp_plan.hpp), the chains' shared blocks from fwd_io /
+// dx_io below; the launchers are in the translation units that hold the kernels:
 //   mlp_fp32.hip  fp32 parity mode: chunk-major forward and backward dX chain
 //   mlp_16.hip    bf16 / fp16: row-block-major forward, dX chain, input gradients
 //   mlp_dw.hip    active-tile flags, the dW GEMM and its deterministic split-M reduction
@@ -41,16 +43,6 @@ bool plan_or_error(const NrMlpConfig* cfg, MlpPlan* p) {
     if (!make_plan(cfg, p, &why)) {
         set_error("NrMlpConfig unsupported: %s", why);
         return false;
-    }
-    return true;
-}
-
-// false when the stream would not fit: the caller fails instead of running on a truncated one
-bool add_stream_layer(StreamDesc& sd, int nchunks, int chunk_kb, int load_kb = -1) {
-    if (sd.nq + nchunks > kMaxChunks) return false;
-    for (int c = 0; c < nchunks; ++c) {
-        sd.ckb[sd.nq] = load_kb < 0 ? chunk_kb : load_kb;
-        sd.cadv[sd.nq++] = chunk_kb;
     }
     return true;
 }
@@ -244,13 +236,9 @@ int nr_mlp_forward(const NrMlpConfig* cfg, const void* packed, const float* para
     }
     FwdArgs a{};
     fwd_io(a, p, packed, params, x, d, M, z.tiles, rgb, sigma, saved, z.saved_off, z.mask_off);
-    a.sd.base = p.lin[0].pk_fwd;
-    for (int l = 0; l < p.n_lin; ++l) {
-        const LinearDesc& dl = p.lin[l];
-        NR_REQUIRE(add_stream_layer(a.sd, dl.KB, dl.NB * p.fpb),
-                   "nr_mlp_forward: the weight stream exceeds kMaxChunks = %d chunks", kMaxChunks);
-        a.vb[l] = dl.vb;
-    }
+    const char* why = "";
+    NR_REQUIRE(fwd_stream(p, &a.sd, &a.slot_bytes, &why), "nr_mlp_forward: %s", why);
+    for (int l = 0; l < p.n_lin; ++l) a.vb[l] = p.lin[l].vb;
     a.vsig = p.vsig;
     a.vrgb = p.vrgb;
     return launch_fwd(p, a, saved != nullptr, s);
@@ -306,19 +294,8 @@ int nr_mlp_backward_dx(const NrMlpConfig* cfg, const void* packed, const float* 
     b.g_x = g_x;
     b.g_d = g_d;
     b.inv_gscale = 1.0f / b.gscale;
-    // a skip layer's W^T chunk is [h rows | x_enc rows] and dir's is [feat rows |
-    // d_enc rows]: without g_x / g_d only the first 8 row blocks are loaded
-    bool stream_fits = true;
-    auto add_T = [&](int l) {
-        const bool partial = !wx && ((l > 0 && l < n && is_skip(p, l - 1)) || l == n + 1);
-        stream_fits &= add_stream_layer(b.sd, p.lin[l].NB, p.lin[l].KB * p.fpb, partial ? kHB * p.fpb : -1);
-    };
-    b.sd.base = p.lin[n + 1].pk_bwd;
-    add_T(n + 1);  // dir^T
-    add_T(n);      // feat^T
-    for (int i = n - 1; i >= 1; --i) add_T(i);
-    if (wx) add_T(0);
-    NR_REQUIRE(stream_fits, "nr_mlp_backward_dx: the weight stream exceeds kMaxChunks = %d chunks", kMaxChunks);
+    const char* why = "";
+    NR_REQUIRE(bwd_stream(p, wx, &b.sd, &b.slot_bytes, &why), "nr_mlp_backward_dx: %s", why);
     b.vsig = p.vsig;
     if (!p.dense_bwd) {
         // the chain writes g_x / g_d of the active tiles only: the rest are exactly zero
@@ -341,75 +318,15 @@ int nr_mlp_backward_dw(const NrMlpConfig* cfg, int64_t M, const void* saved, voi
     NR_REQUIRE((reinterpret_cast<uintptr_t>(saved) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
                "nr_mlp_backward_dw: saved and workspace must be 16-byte aligned");
     if (M == 0) return NR_OK;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
     const MlpSizes z = make_sizes(p, M);
-    const char* sv = static_cast<const char*>(saved);
-    char* ws = static_cast<char*>(workspace);
-    DwArgs w;
-    std::memset(&w, 0, sizeof(w));
-    w.slabs = reinterpret_cast<float*>(ws + z.slab_off);
-    w.tiles = z.tiles;
-    w.list = reinterpret_cast<const uint32_t*>(ws + z.dwlist_off);  // written by nr_mlp_backward_dx
-    w.count = reinterpret_cast<const uint32_t*>(ws + z.count_off);
-    w.njobs = p.n_jobs;
-    int nwg = 0;
-    NR_REQUIRE(p.n_jobs <= 32 && z.max_chunks < 2048, "nr_mlp_backward_dw: %d jobs x %d chunks beyond the map",
-               p.n_jobs, z.max_chunks);
-    for (int c = 0; c < z.max_chunks; ++c)
-        for (int j = 0; j < p.n_jobs; ++j)
-            if (c < z.job_chunks[j]) {
-                NR_REQUIRE(nwg < kDwMaxWgs, "nr_mlp_backward_dw: more than %d workgroups", kDwMaxWgs);
-                w.wg_map[nwg++] = static_cast<uint16_t>(j | c << 5);
-            }
-    for (int j = 0; j < p.n_jobs; ++j) w.job_chunks[j] = z.job_chunks[j];
-    w.slab_floats_per_chunk = p.slab_floats_per_chunk;
-    int max_blk = 0;
-    for (int j = 0; j < p.n_jobs; ++j) {
-        const DwJob& jb = p.job[j];
-        w.job_NBz[j] = jb.NBz;
-        w.job_KB[j] = jb.KB;
-        for (int v = 0; v < kDwWaves; ++v) {
-            if (v >= jb.nwaves) {
-                w.job_wave[j][v] = 0;
-                continue;
-            }
-            const DwWave& sh = jb.w[v];
-            NR_REQUIRE(sh.np >= 1 && sh.np <= kDwMaxP && sh.nq >= 1 && sh.nq <= kDwMaxQ && sh.row0 >= 0 &&
-                           sh.row0 + sh.np <= jb.NBz && sh.col0 >= 0 && sh.col0 + sh.nq <= jb.KB && jb.NBz < 64 &&
-                           jb.KB < 64,
-                       "nr_mlp_backward_dw: job %d wave %d share out of its %dx%d grid", j, v, jb.NBz, jb.KB);
-            w.job_wave[j][v] = dw_wave_pack(sh.row0, sh.np, sh.col0, sh.nq, sh.bias);
-        }
-        int ns = 0;
-        for (int q = 0; q < jb.ndz; ++q, ++ns) {
-            w.seg_ptr[j][ns] = (jb.dz[q].is_ws ? ws : sv) + (jb.dz[q].is_ws ? z.ws_off : z.saved_off)[jb.dz[q].tensor];
-            w.seg_blocks[j][ns] = static_cast<uint8_t>(jb.dz[q].blocks);
-        }
-        for (int q = 0; q < jb.nin; ++q, ++ns) {
-            w.seg_ptr[j][ns] = (jb.in[q].is_ws ? ws : sv) + (jb.in[q].is_ws ? z.ws_off : z.saved_off)[jb.in[q].tensor];
-            w.seg_blocks[j][ns] = static_cast<uint8_t>(jb.in[q].blocks);
-        }
-        w.job_slab[j] = jb.slab_off;
-        NR_REQUIRE((jb.NBz + jb.KB) * p.fpb <= kDwWaves * dw_max_pieces(p.fpb == 2),
-                   "nr_mlp_backward_dw: job %d stages %d blocks, beyond the kernel's per-wave pieces", j, jb.NBz + jb.KB);
-        max_blk = jb.NBz + jb.KB > max_blk ? jb.NBz + jb.KB : max_blk;
-    }
-    w.stage_bytes = max_blk * p.fpb * kFragBytes;
-    // as many stages as fit in 160 KiB (+1 KB scratch): 4 for bf16, 2 for fp32
-    w.nstage = static_cast<int>((160 * 1024 - kFragBytes) / w.stage_bytes);
-    if (w.nstage > NR_DW_NSTAGE) w.nstage = NR_DW_NSTAGE;
-    size_t lds = static_cast<size_t>(w.nstage) * w.stage_bytes + kFragBytes;
-    // the largest chunk's list entries behind the stages, when they fit
-    int min_chunks = z.job_chunks[0];
-    for (int j = 1; j < p.n_jobs; ++j) min_chunks = z.job_chunks[j] < min_chunks ? z.job_chunks[j] : min_chunks;
-    const size_t list_bytes = (static_cast<size_t>(ceil_div_ll(z.tiles, min_chunks)) * 4 + 15) / 16 * 16;
-    if (lds + list_bytes <= 160 * 1024) {
-        w.list_lds = static_cast<int>(lds);
-        lds += list_bytes;
-    }
-    NR_REQUIRE(w.nstage >= 2, "nr_mlp_backward_dw: a %d-byte stage does not fit twice in LDS", w.stage_bytes);
-    NR_REQUIRE(lds <= 160 * 1024, "nr_mlp_backward_dw: %zu bytes of LDS staging exceeds 160 KiB", lds);
-    return launch_dw(p.prec, w, nwg, lds, s);
+    NR_REQUIRE(z.max_chunks < 2048, "nr_mlp_backward_dw: %d chunks beyond the workgroup map", z.max_chunks);
+    DwArgs w;  // the list and count: written by nr_mlp_backward_dx
+    int nwg;
+    size_t lds;
+    const char* why = "";
+    NR_REQUIRE(dw_args(p, z, static_cast<const char*>(saved), static_cast<char*>(workspace), &w, &nwg, &lds, &why),
+               "nr_mlp_backward_dw: %s", why);
+    return launch_dw(p.prec, w, nwg, lds, static_cast<hipStream_t>(stream));
 }
 
 int nr_mlp_backward_reduce(const NrMlpConfig* cfg, int64_t M, const void* workspace, float* g_params,
@@ -422,33 +339,8 @@ int nr_mlp_backward_reduce(const NrMlpConfig* cfg, int64_t M, const void* worksp
         (void)hipMemsetAsync(g_params, 0, sizeof(float) * p.param_count, s);
         return check_launch("nr_mlp_backward_reduce");
     }
-    const MlpSizes z = make_sizes(p, M);
     ReduceArgs r;
-    std::memset(&r, 0, sizeof(r));
-    r.slabs = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + z.slab_off);
-    r.g = g_params;
-    r.inv_gscale = 1.0f / grad_scale(p.prec);
-    r.param_count = p.param_count;
-    r.slab_floats_per_chunk = p.slab_floats_per_chunk;
-    r.n_red = p.n_red;
-    for (int k = 0; k < p.n_red; ++k) {
-        const ReduceRange& rr = p.red[k];
-        r.rows[k] = rr.rows;
-        r.in[k] = rr.in;
-        r.nseg[k] = rr.nseg;
-        r.bjob[k] = rr.bjob;
-        r.brow0[k] = rr.brow0;
-        r.w_off[k] = rr.w_off;
-        r.b_off[k] = rr.b_off;
-        for (int q = 0; q < rr.nseg; ++q) r.seg[k][q] = rr.seg[q];
-    }
-    for (int j = 0; j < p.n_jobs; ++j) {
-        r.job_slab[j] = p.job[j].slab_off;
-        r.job_KB[j] = p.job[j].KB;
-        r.job_chunks[j] = z.job_chunks[j];
-    }
-    int max_rows = 1;
-    for (int k = 0; k < p.n_red; ++k) max_rows = p.red[k].rows > max_rows ? p.red[k].rows : max_rows;
+    const int max_rows = reduce_args(p, make_sizes(p, M), static_cast<const char*>(workspace), g_params, &r);
     return launch_dw_reduce(r, max_rows, s);
 }
 

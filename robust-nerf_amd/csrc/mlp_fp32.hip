@@ -638,23 +638,8 @@ __global__ __launch_bounds__(kNT, 1) void mlp_bwd_kernel(BwdArgs a) {
 }
 
 // ----------------------------------------------------------- launchers -----
-namespace {
-
-int max_chunk(const StreamDesc& sd) {
-    int m = 0;
-    for (int q = 0; q < sd.nq; ++q) m = sd.ckb[q] * 1024 > m ? sd.ckb[q] * 1024 : m;
-    return m;
-}
-
-}  // namespace
-
-int launch_fwd(const MlpPlan& p, FwdArgs& a, bool train, hipStream_t s) {
-    // the stream's two LDS slots, each the largest chunk: 8 row blocks of a layer's W, 32 KB
-    a.slot_bytes = max_chunk(a.sd);
-    if (a.slot_bytes > 32 * 1024) {
-        set_error("nr_mlp_forward: chunk of %d bytes exceeds the stager", a.slot_bytes);
-        return NR_EARG;
-    }
+int launch_fwd(const MlpPlan& p, const FwdArgs& a, bool train, hipStream_t s) {
+    // the stream's two LDS slots (fwd_stream, mlp_plan.hpp)
     const size_t lds = 2 * static_cast<size_t>(a.slot_bytes);
     const dim3 grid(static_cast<unsigned>(ceil_div_ll(a.tiles, kNT / 64))), block(kNT);
     const bool found = dispatch_model(p, [&](auto xb, auto db) {
@@ -671,13 +656,7 @@ int launch_fwd(const MlpPlan& p, FwdArgs& a, bool train, hipStream_t s) {
     return check_launch("nr_mlp_forward");
 }
 
-int launch_bwd(const MlpPlan& p, BwdArgs& a, bool want_x, hipStream_t s) {
-    // the largest chunk is the skip layer's W^T: (XB + 8) row blocks, at most 40 KB
-    a.slot_bytes = max_chunk(a.sd);
-    if (a.slot_bytes > 40 * 1024) {
-        set_error("nr_mlp_backward_dx: chunk of %d bytes exceeds the stager", a.slot_bytes);
-        return NR_EARG;
-    }
+int launch_bwd(const MlpPlan& p, const BwdArgs& a, bool want_x, hipStream_t s) {
     const size_t lds = 2 * static_cast<size_t>(a.slot_bytes);
     // every part of every segment (select_tile's workgroup mapping)
     const dim3 grid(static_cast<unsigned>(a.nseg * (kSegTiles / (kNT / 64)))), block(kNT);

@@ -1,5 +1,7 @@
 // Between mlp.hip (the extern "C" entry points, which fill these argument structs from
-// the plan) and the translation units that hold the kernels and launch them.
+// the plan) and the translation units that hold the kernels and launch them.  The
+// descriptors that are functions of the plan alone (StreamDesc, DwArgs, ReduceArgs) and
+// their builders are host-only code in mlp_plan.hpp; what needs HIP types is here.
 #pragma once
 
 #include <type_traits>
@@ -11,21 +13,7 @@
 #pragma GCC visibility push(hidden)  // the launchers are internal to the library
 namespace nr {
 
-// fp16 backward runs on dz scaled by 2^14 (the per-sample gradients of a mean
-// loss over 4096 rays sit near 1e-6, in fp16's subnormal range); the dW reduce and
-// the input gradients divide it out exactly.
-inline float grad_scale(int prec) { return prec == NR_PREC_FP16 ? 16384.0f : 1.0f; }
-
 // ------------------------------------------- fp32, chunk-major (mlp_fp32.hip) ----
-// The weight stream: a sequence of chunks (all row blocks of one k block of one layer
-// image) consumed in order; at most kMaxChunks of them (mlp_plan.hpp).
-struct StreamDesc {
-    int64_t base;                  // byte offset of the stream's first chunk in `packed`
-    int nq;                        // chunks
-    int ckb[kMaxChunks];           // bytes loaded per chunk, in KB
-    int cadv[kMaxChunks];          // bytes to the next chunk, in KB (>= ckb: a chunk may be loaded in part)
-};
-
 // What every forward chain reads and writes.  fwd_io() (mlp.hip) is the one place that
 // assigns these fields, in whichever argument struct holds them: the 16-bit structs derive
 // from the block, the fp32 structs restate its fields in an order of their own (below).
@@ -127,9 +115,10 @@ struct BwdArgs {
     int ws_feat, ws_dir, ws_heads;
 };
 
-// train: save the activations; want_x: also compute g_x / g_d.  Both set a.slot_bytes.
-int launch_fwd(const MlpPlan& p, FwdArgs& a, bool train, hipStream_t s);
-int launch_bwd(const MlpPlan& p, BwdArgs& a, bool want_x, hipStream_t s);
+// train: save the activations; want_x: also compute g_x / g_d.  a.sd and a.slot_bytes are
+// fwd_stream's / bwd_stream's (mlp_plan.hpp).
+int launch_fwd(const MlpPlan& p, const FwdArgs& a, bool train, hipStream_t s);
+int launch_bwd(const MlpPlan& p, const BwdArgs& a, bool want_x, hipStream_t s);
 
 // ------------------------------------- 16-bit, row-block major (mlp_16.hip) ----
 struct RbmArgs : FwdIO {
@@ -184,54 +173,6 @@ auto dispatch_prec16(int prec, F&& f) {
 }
 
 // --------------------------------------- active tiles, dW, reduce (mlp_dw.hip) ----
-#ifndef NR_DW_NSTAGE
-#define NR_DW_NSTAGE 4  // LDS staging ring depth of the dW kernel (tiles)
-#endif
-constexpr int kDwThreads = 512;
-constexpr int kDwWaves = kDwThreads / 64;
-static_assert(kDwWaves == kDwMaxWaves, "dW wave shares are planned for 8-wave workgroups");
-
-constexpr int kDwMaxWgs = 256;  // one round of workgroups (make_sizes: NR_DW_WGS)
-struct DwArgs {
-    float* slabs;
-    int njobs;
-    int64_t tiles;
-    const uint32_t* list;           // active tiles in order and their count (built during the dX launch)
-    const uint32_t* count;
-    int list_lds;                   // LDS byte offset the chunk's list entries are staged to (0: read them global)
-    int job_chunks[kMaxJobs];       // chunks of each job: list entries split evenly in order
-    uint16_t wg_map[kDwMaxWgs];     // workgroup -> job | chunk << 5 (chunk-major: one chunk of every job in a row)
-    int stage_bytes, nstage;
-    int64_t slab_floats_per_chunk;
-    int job_NBz[kMaxJobs], job_KB[kMaxJobs];
-    int64_t job_slab[kMaxJobs];
-    const char* seg_ptr[kMaxJobs][2 * kMaxJobSeg];  // tensor region: dz segments, then inputs
-    uint8_t seg_blocks[kMaxJobs][2 * kMaxJobSeg];
-    // wave share (DwWave) packed: row0 | np << 6 | col0 << 9 | nq << 15 | bias << 17; 0 = idle
-    int job_wave[kMaxJobs][kDwWaves];
-};
-static_assert(sizeof(DwArgs) <= 4096, "dW kernel arguments exceed 4 KiB");
-
-__host__ __device__ constexpr int dw_wave_pack(int row0, int np, int col0, int nq, int bias) {
-    return row0 | np << 6 | col0 << 9 | nq << 15 | bias << 17;
-}
-
-// g_params[param] = sum over chunks of its slab entry (fixed chunk order: deterministic).
-struct ReduceArgs {
-    const float* slabs;
-    float* g;
-    float inv_gscale;  // fp16: undo the backward's loss scale (a power of two: exact)
-    int64_t param_count;
-    int64_t slab_floats_per_chunk;
-    int n_red;
-    int rows[kMaxRed], in[kMaxRed], nseg[kMaxRed], bjob[kMaxRed], brow0[kMaxRed];
-    int64_t w_off[kMaxRed], b_off[kMaxRed];
-    RedSeg seg[kMaxRed][kMaxSeg];
-    int64_t job_slab[kMaxJobs];
-    int job_KB[kMaxJobs];
-    int job_chunks[kMaxJobs];  // slab sets of each job, summed in chunk order
-};
-
 int launch_tile_flags(const float* g_rgb, const float* g_sigma, int64_t M, int dense, int64_t nseg, uint8_t* flags,
                       uint32_t* blk_count, hipStream_t s);
 int launch_dw(int prec, const DwArgs& a, int nwg, size_t lds, hipStream_t s);

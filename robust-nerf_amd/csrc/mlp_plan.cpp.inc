@@ -179,8 +179,11 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
     // h_{n-1}) and the dir job the rgb head ([dz_dir, dz_heads] x [feat, d_enc, h_c]),
     // so h_{n-1} is read once.
     int64_t slab = 0;
-    int nj = 0;
+    int nj = 0, max_blk = 0;
     bool fits = true;
+    // what the dW kernel assumes of every job, checked as the jobs and shares are made: grids
+    // and shares inside dw_wave_pack's fields, a stage its waves can issue and LDS holds twice
+    bool packs = true, stages = true;
     auto add_job = [&](int ndz, const DwSeg* dz, int nin, const DwSeg* in) {
         if (nj == kMaxJobs) {  // the caller's shares go to a scratch job; the plan fails
             fits = false;
@@ -199,23 +202,29 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
             j.in[s] = in[s];
             j.KB += in[s].blocks;
         }
+        packs = packs && j.NBz < 64 && j.KB < 64;
+        stages = stages && (j.NBz + j.KB) * p->fpb <= dw_max_stage_pieces(p->fpb == 2);
+        max_blk = j.NBz + j.KB > max_blk ? j.NBz + j.KB : max_blk;
         j.slab_off = slab;
         slab += static_cast<int64_t>(j.NBz) * 32 * (j.KB * 32 + 1);
         j.nwaves = 0;
         return nj++;
     };
+    auto add_share = [&](DwJob& jb, const DwWave& sh) {
+        if (jb.nwaves == kDwMaxWaves) {
+            fits = false;
+            return;
+        }
+        packs = packs && sh.np >= 1 && sh.np <= kDwMaxP && sh.nq >= 1 && sh.nq <= kDwMaxQ && sh.row0 >= 0 &&
+                sh.row0 + sh.np <= jb.NBz && sh.col0 >= 0 && sh.col0 + sh.nq <= jb.KB;
+        jb.w[jb.nwaves++] = sh;
+    };
     // wave shares: rows [r0, r1) x cols [c0, c1) in 4 x 2 pieces, bias on the first column piece
     auto add_waves = [&](int j, int r0, int r1, int c0, int c1, bool bias) {
-        DwJob& jb = p->job[j];
         for (int c = c0; c < c1; c += kDwMaxQ)
-            for (int r = r0; r < r1; r += 4) {
-                if (jb.nwaves == kDwMaxWaves) {
-                    fits = false;
-                    return;
-                }
-                jb.w[jb.nwaves++] = {r, r1 - r < 4 ? r1 - r : 4, c, c1 - c < kDwMaxQ ? c1 - c : kDwMaxQ,
-                                     bias && c == c0 ? 1 : 0};
-            }
+            for (int r = r0; r < r1; r += 4)
+                add_share(p->job[j], {r, r1 - r < 4 ? r1 - r : 4, c, c1 - c < kDwMaxQ ? c1 - c : kDwMaxQ,
+                                      bias && c == c0 ? 1 : 0});
     };
     int xjob[kMaxTrunk], xrow[kMaxTrunk], hjob[kMaxTrunk];
     {
@@ -223,9 +232,9 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
         for (int i = 0; i < n; ++i)
             if (i == 0 || is_skip(*p, i - 1)) layers[nx++] = i;
         // as many x-layers per job as its staged blocks allow: (cnt*kHB + XB) * FPB
-        // pieces over 8 waves (dw_max_pieces each), and its shares 8 waves
+        // pieces (dw_max_stage_pieces), and its shares 8 waves
         int per = kMaxJobSeg;
-        while (per > 1 && ((per * kHB + p->XB) * p->fpb > kDwMaxWaves * dw_max_pieces(p->fpb == 2) ||
+        while (per > 1 && ((per * kHB + p->XB) * p->fpb > dw_max_stage_pieces(p->fpb == 2) ||
                            per * (kHB / 4) * ((p->XB + kDwMaxQ - 1) / kDwMaxQ) > kDwMaxWaves))
             --per;
         for (int a = 0; a < nx; a += per) {
@@ -255,8 +264,8 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
         DwSeg in[1] = {{0, SV_H0 + n - 1, kHB}};
         jfeat = add_job(2, dz, 1, in);
         DwJob& jb = p->job[jfeat];
-        for (int c = 0; c < kHB; c += kDwMaxQ) jb.w[jb.nwaves++] = {0, 4, c, kDwMaxQ, c == 0 ? 1 : 0};
-        for (int c = 0; c < kHB; c += kDwMaxQ) jb.w[jb.nwaves++] = {4, kHB + 1 - 4, c, kDwMaxQ, c == 0 ? 1 : 0};
+        for (int c = 0; c < kHB; c += kDwMaxQ) add_share(jb, {0, 4, c, kDwMaxQ, c == 0 ? 1 : 0});
+        for (int c = 0; c < kHB; c += kDwMaxQ) add_share(jb, {4, kHB + 1 - 4, c, kDwMaxQ, c == 0 ? 1 : 0});
         jsig = jfeat;
     } else {
         // fp32 is MFMA-bound in dW, and a SIMD's two waves' blocks set its time: the
@@ -287,6 +296,18 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
                "ceil((len(skips) + 1) / 2) must not exceed 23, or 22 in fp32)";
         return false;
     }
+    if (!packs) {
+        *why = "a dW wave share lies outside its job's grid of at most 63 x 63 blocks";
+        return false;
+    }
+    if (!stages) {
+        *why = "a dW job stages more blocks per tile than its waves issue or LDS holds twice";
+        return false;
+    }
+    p->dw_stage_bytes = max_blk * p->fpb * kFragBytes;
+    // as many stages as fit beside the 1 KB of scratch: 4 for bf16, 2 for fp32
+    p->dw_nstage = (kDwLdsBytes - kFragBytes) / p->dw_stage_bytes;
+    if (p->dw_nstage > NR_DW_NSTAGE) p->dw_nstage = NR_DW_NSTAGE;
     int red = 0;
     auto add_red = [&](int rows, int in, int64_t w_off, int64_t b_off, int bjob, int brow0) -> ReduceRange& {
         ReduceRange& r = p->red[red++];
@@ -328,7 +349,10 @@ bool make_plan(const NrMlpConfig* c, MlpPlan* p, const char** why) {
     p->n_jobs = nj;
     p->n_red = red;
     p->slab_floats_per_chunk = slab;
-    return true;
+    if (p->prec != NR_PREC_FP32) return true;
+    int slot;  // the chunk-major chains' weight streams, counted and not built
+    return fwd_stream(*p, nullptr, &slot, why) && bwd_stream(*p, true, nullptr, &slot, why) &&
+           bwd_stream(*p, false, nullptr, &slot, why);
 }
 
 static int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
@@ -457,6 +481,143 @@ DinOffsets din_offsets(const MlpPlan& p, const FrozenSizes& f) {
     for (int l = 0; l < p.n_layers; ++l) o.dz_off[l] = f.dz_off[l];  // 0 outside keep_dz
     o.dz_dir_off = f.dz_dir_off;
     return o;
+}
+
+// ---------------------------------------------------------- launch descriptors ----
+namespace {
+// A weight stream in the making: its chunk count and largest load, and with `sd` its table
+struct StreamFill {
+    StreamDesc* sd;
+    int nq, slot_kb;
+    bool fits;
+
+    // a layer's chunks behind the stream's, unless they pass kMaxChunks
+    void push(int nchunks, int chunk_kb, int load_kb) {
+        fits = fits && nq + nchunks <= kMaxChunks;
+        if (!fits) return;
+        for (int c = 0; sd && c < nchunks; ++c) {
+            sd->ckb[nq + c] = load_kb;
+            sd->cadv[nq + c] = chunk_kb;
+        }
+        nq += nchunks;
+        slot_kb = load_kb > slot_kb ? load_kb : slot_kb;
+    }
+
+    bool close(int64_t base, int slot_max, int* slot_bytes, const char** why) {
+        if (!fits) {
+            *why = "an fp32 weight stream has more than kMaxChunks chunks";
+            return false;
+        }
+        if (slot_kb * 1024 > slot_max) {
+            *why = "a chunk of an fp32 weight stream exceeds its LDS slot";
+            return false;
+        }
+        if (sd) {
+            sd->base = base;
+            sd->nq = nq;
+        }
+        *slot_bytes = slot_kb * 1024;
+        return true;
+    }
+};
+}  // namespace
+
+bool fwd_stream(const MlpPlan& p, StreamDesc* sd, int* slot_bytes, const char** why) {
+    StreamFill f{sd, 0, 0, true};
+    for (int l = 0; l < p.n_lin; ++l) f.push(p.lin[l].KB, p.lin[l].NB * p.fpb, p.lin[l].NB * p.fpb);
+    return f.close(p.lin[0].pk_fwd, kFwdSlotMax, slot_bytes, why);
+}
+
+bool bwd_stream(const MlpPlan& p, bool want_x, StreamDesc* sd, int* slot_bytes, const char** why) {
+    const int n = p.n_layers;
+    StreamFill f{sd, 0, 0, true};
+    for (int l = n + 1; l >= (want_x ? 0 : 1); --l) {  // dir^T, feat^T, trunk n-1 .. 1 [, 0]
+        const bool partial = !want_x && ((l > 0 && l < n && is_skip(p, l - 1)) || l == n + 1);
+        f.push(p.lin[l].NB, p.lin[l].KB * p.fpb, partial ? kHB * p.fpb : p.lin[l].KB * p.fpb);
+    }
+    return f.close(p.lin[n + 1].pk_bwd, kBwdSlotMax, slot_bytes, why);
+}
+
+bool dw_args(const MlpPlan& p, const MlpSizes& z, const char* saved, char* workspace, DwArgs* w, int* nwg,
+             size_t* lds, const char** why) {
+    std::memset(w, 0, sizeof(*w));
+    w->slabs = reinterpret_cast<float*>(workspace + z.slab_off);
+    w->tiles = z.tiles;
+    w->list = reinterpret_cast<const uint32_t*>(workspace + z.dwlist_off);
+    w->count = reinterpret_cast<const uint32_t*>(workspace + z.count_off);
+    w->njobs = p.n_jobs;
+    *nwg = 0;
+    for (int c = 0; c < z.max_chunks; ++c)
+        for (int j = 0; j < p.n_jobs; ++j)
+            if (c < z.job_chunks[j]) {
+                if (*nwg == kDwMaxWgs) {
+                    *why = "the dW chunks make more than kDwMaxWgs = 256 workgroups";
+                    return false;
+                }
+                w->wg_map[(*nwg)++] = static_cast<uint16_t>(j | c << 5);
+            }
+    w->slab_floats_per_chunk = p.slab_floats_per_chunk;
+    int min_chunks = z.job_chunks[0];
+    for (int j = 0; j < p.n_jobs; ++j) {
+        const DwJob& jb = p.job[j];
+        w->job_chunks[j] = z.job_chunks[j];
+        min_chunks = z.job_chunks[j] < min_chunks ? z.job_chunks[j] : min_chunks;
+        w->job_NBz[j] = jb.NBz;
+        w->job_KB[j] = jb.KB;
+        w->job_slab[j] = jb.slab_off;
+        for (int v = 0; v < jb.nwaves; ++v)  // the other waves idle: 0
+            w->job_wave[j][v] = dw_wave_pack(jb.w[v].row0, jb.w[v].np, jb.w[v].col0, jb.w[v].nq, jb.w[v].bias);
+        int ns = 0;
+        auto add_seg = [&](const DwSeg& sg) {
+            w->seg_ptr[j][ns] = sg.is_ws ? workspace + z.ws_off[sg.tensor] : saved + z.saved_off[sg.tensor];
+            w->seg_blocks[j][ns++] = static_cast<uint8_t>(sg.blocks);
+        };
+        for (int q = 0; q < jb.ndz; ++q) add_seg(jb.dz[q]);
+        for (int q = 0; q < jb.nin; ++q) add_seg(jb.in[q]);
+    }
+    w->stage_bytes = p.dw_stage_bytes;
+    w->nstage = p.dw_nstage;
+    *lds = static_cast<size_t>(w->nstage) * w->stage_bytes + kFragBytes;
+    // the largest chunk's list entries behind the stages, when they fit
+    const size_t list_bytes = (static_cast<size_t>((z.tiles + min_chunks - 1) / min_chunks) * 4 + 15) / 16 * 16;
+    if (*lds + list_bytes <= static_cast<size_t>(kDwLdsBytes)) {
+        w->list_lds = static_cast<int>(*lds);
+        *lds += list_bytes;
+    }
+    if (*lds > static_cast<size_t>(kDwLdsBytes)) {
+        *why = "the dW staging exceeds kDwLdsBytes = 160 KiB of LDS";
+        return false;
+    }
+    return true;
+}
+
+int reduce_args(const MlpPlan& p, const MlpSizes& z, const char* workspace, float* g_params, ReduceArgs* r) {
+    std::memset(r, 0, sizeof(*r));
+    r->slabs = reinterpret_cast<const float*>(workspace + z.slab_off);
+    r->g = g_params;
+    r->inv_gscale = 1.0f / grad_scale(p.prec);
+    r->param_count = p.param_count;
+    r->slab_floats_per_chunk = p.slab_floats_per_chunk;
+    r->n_red = p.n_red;
+    int max_rows = 1;
+    for (int k = 0; k < p.n_red; ++k) {
+        const ReduceRange& rr = p.red[k];
+        r->rows[k] = rr.rows;
+        r->in[k] = rr.in;
+        r->nseg[k] = rr.nseg;
+        r->bjob[k] = rr.bjob;
+        r->brow0[k] = rr.brow0;
+        r->w_off[k] = rr.w_off;
+        r->b_off[k] = rr.b_off;
+        for (int q = 0; q < rr.nseg; ++q) r->seg[k][q] = rr.seg[q];
+        max_rows = rr.rows > max_rows ? rr.rows : max_rows;
+    }
+    for (int j = 0; j < p.n_jobs; ++j) {
+        r->job_slab[j] = p.job[j].slab_off;
+        r->job_KB[j] = p.job[j].KB;
+        r->job_chunks[j] = z.job_chunks[j];
+    }
+    return max_rows;
 }
 
 }  // namespace nr

@@ -15,6 +15,7 @@
 // ReLU masks are bitmasks in accumulator-register order (16 B per lane per layer).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #include "nerf_hip.h"
@@ -32,13 +33,25 @@ constexpr int kMaxJobs = kMaxTrunk + 8;  // dW jobs: x-jobs + trunk h-jobs + fea
 constexpr int kMaxSeg = 2;
 constexpr int kMaxJobSeg = 4;            // tensors on either side of a dW job
 constexpr int kMaxRed = kMaxTrunk + 4;    // reduce ranges: trunk, feat, sigma, rgb, dir
-// fp32 weight streams (StreamDesc, mlp_launch.hpp): chunks per stream, >= the sum of KB
-// (forward) or NB (backward) over the MFMA layers of every config make_plan accepts
-// (tests/native/plan_check.cpp sweeps it; the entry points refuse a stream that does not fit)
+// fp32 weight streams (StreamDesc below): chunks per stream, >= the sum of KB (forward) or
+// NB (backward) over the MFMA layers of every config make_plan accepts: the stream builders
+// refuse a stream that does not fit, so make_plan refuses its config
 constexpr int kMaxChunks = 176;
-// dW staging: each of the 8 waves issues at most this many 1-KB LDS-DMA pieces
-// per tile, so a job's (NBz + KB) * FPB blocks must not exceed 8x it
+// dW workgroups: 8 waves, each issuing at most dw_max_pieces 1-KB LDS-DMA pieces per tile
+constexpr int kDwThreads = 512;
+constexpr int kDwWaves = kDwThreads / 64;
 __host__ __device__ constexpr int dw_max_pieces(bool k16) { return k16 ? 6 : 10; }
+constexpr int kDwMaxWgs = 256;          // one round of workgroups (make_sizes: NR_DW_WGS)
+constexpr int kDwLdsBytes = 160 * 1024;  // a workgroup's LDS: the staging ring, 1 KB of scratch, the chunk's list
+#ifndef NR_DW_NSTAGE
+#define NR_DW_NSTAGE 4  // LDS staging ring depth of the dW kernel (tiles)
+#endif
+// The 1-KB pieces a dW job may stage per tile, (NBz + KB) * FPB of them: what its waves can
+// issue, and a stage must fit twice in LDS beside the scratch (the ring needs two)
+constexpr int dw_max_stage_pieces(bool k16) {
+    constexpr int twice = (kDwLdsBytes - kFragBytes) / (2 * kFragBytes);
+    return kDwWaves * dw_max_pieces(k16) < twice ? kDwWaves * dw_max_pieces(k16) : twice;
+}
 
 // One input segment of a linear layer: columns [col0, col0+width) of W,
 // occupying ceil(width/32) consecutive 32-wide input blocks.
@@ -66,7 +79,7 @@ struct DwSeg {
 // One wave's share of a dW job: dz row blocks [row0, row0+np) x input column
 // blocks [col0, col0+nq) (np <= kDwMaxP, nq <= kDwMaxQ), plus the bias partial
 // sums of those dz rows when bias != 0.
-constexpr int kDwMaxWaves = 8;
+constexpr int kDwMaxWaves = kDwWaves;
 constexpr int kDwMaxP = 5, kDwMaxQ = 2;
 struct DwWave {
     int row0, np, col0, nq, bias;
@@ -130,6 +143,7 @@ struct MlpPlan {
     // dW jobs and the reduction map
     int n_jobs;
     DwJob job[kMaxJobs];
+    int dw_stage_bytes, dw_nstage;    // the dW staging ring: the largest job's blocks of one tile, 2..NR_DW_NSTAGE times
     int64_t slab_floats_per_chunk;
     int n_red;
     ReduceRange red[kMaxRed];
@@ -137,21 +151,15 @@ struct MlpPlan {
 
 inline bool is_skip(const MlpPlan& p, int i) { return (p.skips >> i) & 1u; }
 
-// Chunks of the fp32 weight streams as the entry points build them: the forward streams
-// every k block of every W image, the backward (with input gradients) every row block of
-// every W^T image.
-inline int fwd_stream_chunks(const MlpPlan& p) {
-    int n = 0;
-    for (int l = 0; l < p.n_lin; ++l) n += p.lin[l].KB;
-    return n;
-}
-inline int bwd_stream_chunks(const MlpPlan& p) {
-    int n = 0;
-    for (int l = 0; l < p.n_lin; ++l) n += p.lin[l].NB;
-    return n;
-}
+// fp16 backward runs on dz scaled by 2^14 (the per-sample gradients of a mean
+// loss over 4096 rays sit near 1e-6, in fp16's subnormal range); the dW reduce and
+// the input gradients divide it out exactly.
+inline float grad_scale(int prec) { return prec == NR_PREC_FP16 ? 16384.0f : 1.0f; }
 
-// Builds the plan; returns false (with *why set) for unsupported configs.
+// Builds the plan; returns false (with *why set) for unsupported configs: everything about a
+// launch that the config alone decides is checked here (the fp32 weight streams, the dW
+// shares and staging), so a config that gets a plan has a launch at every M but those the
+// entry points refuse by M.
 bool make_plan(const NrMlpConfig* cfg, MlpPlan* p, const char** why);
 
 // Byte sizes / offsets that depend on the number of samples.
@@ -218,5 +226,86 @@ struct DinOffsets {
 
 DinOffsets din_offsets(const MlpPlan& p, const MlpSizes& z);
 DinOffsets din_offsets(const MlpPlan& p, const FrozenSizes& f);  // 16-bit (fp32 has the training layout)
+
+// ---------------------------------------------------------- launch descriptors ----
+// What the fp32 chains, the dW GEMM and its reduction take of the plan, each built by one
+// pure function of (plan, sizes, base pointers) that the entry points (mlp.hip) launch with
+// and the host checker (tests/native/plan_check.cpp) inspects.  The structs are kernel
+// arguments: their layout is the kernels'.
+
+// An fp32 weight stream: a sequence of chunks (all row blocks of one k block of one layer
+// image) consumed in order through two LDS slots of the largest chunk's size.
+struct StreamDesc {
+    int64_t base;                  // byte offset of the stream's first chunk in `packed`
+    int nq;                        // chunks
+    int ckb[kMaxChunks];           // bytes loaded per chunk, in KB
+    int cadv[kMaxChunks];          // bytes to the next chunk, in KB (>= ckb: a chunk may be loaded in part)
+};
+// the forward's largest chunk is 8 row blocks of a layer's W; the backward's the skip
+// layer's W^T, (XB + 8) row blocks
+constexpr int kFwdSlotMax = 32 * 1024, kBwdSlotMax = 40 * 1024;
+
+// The forward stream (W images: trunk 0..n-1, feat, dir) and the backward stream (W^T
+// images: dir, feat, trunk n-1..1, and trunk 0 when want_x), with *slot_bytes the size of an
+// LDS slot.  Without want_x a skip layer's and the dir layer's chunks are loaded in part:
+// [h rows | x_enc rows] and [feat rows | d_enc rows], of which only the first 8 row blocks
+// feed anything but g_x / g_d.  false (with *why) for a stream of more than kMaxChunks chunks
+// or a slot beyond kFwdSlotMax / kBwdSlotMax.  make_plan calls them with a null sd, which
+// checks the same without writing a table, and refuses an fp32 config they refuse.
+bool fwd_stream(const MlpPlan& p, StreamDesc* sd, int* slot_bytes, const char** why);
+bool bwd_stream(const MlpPlan& p, bool want_x, StreamDesc* sd, int* slot_bytes, const char** why);
+
+struct DwArgs {
+    float* slabs;
+    int njobs;
+    int64_t tiles;
+    const uint32_t* list;           // active tiles in order and their count (built during the dX launch)
+    const uint32_t* count;
+    int list_lds;                   // LDS byte offset the chunk's list entries are staged to (0: read them global)
+    int job_chunks[kMaxJobs];       // chunks of each job: list entries split evenly in order
+    uint16_t wg_map[kDwMaxWgs];     // workgroup -> job | chunk << 5 (chunk-major: one chunk of every job in a row)
+    int stage_bytes, nstage;
+    int64_t slab_floats_per_chunk;
+    int job_NBz[kMaxJobs], job_KB[kMaxJobs];
+    int64_t job_slab[kMaxJobs];
+    const char* seg_ptr[kMaxJobs][2 * kMaxJobSeg];  // tensor region: dz segments, then inputs
+    uint8_t seg_blocks[kMaxJobs][2 * kMaxJobSeg];
+    // wave share (DwWave) packed: row0 | np << 6 | col0 << 9 | nq << 15 | bias << 17; 0 = idle
+    int job_wave[kMaxJobs][kDwWaves];
+};
+static_assert(sizeof(DwArgs) <= 4096, "dW kernel arguments exceed 4 KiB");
+static_assert(kMaxJobs <= 32, "wg_map holds the job in 5 bits");
+
+// make_plan keeps row0, col0 and their ends below 64, np <= kDwMaxP and nq <= kDwMaxQ
+__host__ __device__ constexpr int dw_wave_pack(int row0, int np, int col0, int nq, int bias) {
+    return row0 | np << 6 | col0 << 9 | nq << 15 | bias << 17;
+}
+
+// The dW launch over `saved` and `workspace` (16-byte aligned; the list and count are what
+// nr_mlp_backward_dx left in the workspace): *w, *nwg workgroups, *lds bytes of dynamic LDS
+// (the staging ring, 1 KB of scratch and, when they fit, the largest chunk's list entries).
+// false (with *why) when z's chunks make more than kDwMaxWgs workgroups or more LDS than
+// kDwLdsBytes; z.max_chunks must be below 2048 (wg_map's 11 bits).
+bool dw_args(const MlpPlan& p, const MlpSizes& z, const char* saved, char* workspace, DwArgs* w, int* nwg,
+             size_t* lds, const char** why);
+
+// g_params[param] = sum over chunks of its slab entry (fixed chunk order: deterministic).
+struct ReduceArgs {
+    const float* slabs;
+    float* g;
+    float inv_gscale;  // fp16: undo the backward's loss scale (a power of two: exact)
+    int64_t param_count;
+    int64_t slab_floats_per_chunk;
+    int n_red;
+    int rows[kMaxRed], in[kMaxRed], nseg[kMaxRed], bjob[kMaxRed], brow0[kMaxRed];
+    int64_t w_off[kMaxRed], b_off[kMaxRed];
+    RedSeg seg[kMaxRed][kMaxSeg];
+    int64_t job_slab[kMaxJobs];
+    int job_KB[kMaxJobs];
+    int job_chunks[kMaxJobs];  // slab sets of each job, summed in chunk order
+};
+
+// The reduce launch over the slabs dw_args' launch wrote; returns the longest range's rows
+int reduce_args(const MlpPlan& p, const MlpSizes& z, const char* workspace, float* g_params, ReduceArgs* r);
 
 }  // namespace nr

@@ -275,7 +275,9 @@ def _check_supported(cfg: NrMlpConfig, config: ModelConfig, n_params: int) -> No
     skips at layers 0..depth-2, as many as the dW job table holds: depth +
     ceil((len(skips) + 1) / 2) <= 23 (22 in fp32), which only bites at depths 15 and 16
     (tests/test_plan.py sweeps it).  The plan check is host code (nr_mlp_packed_bytes), so this runs
-    without a GPU."""
+    without a GPU, and it is the whole check: make_plan (csrc/mlp_plan.cpp.inc) also refuses a
+    config whose fp32 weight streams, dW wave shares or dW staging the kernels could not launch
+    with, so after construction an entry point refuses only by its pointers or by M."""
     lib = _hip.load()
     if int(lib.nr_mlp_packed_bytes(ctypes.byref(cfg))) < 0:
         raise NotImplementedError(

@@ -1,6 +1,8 @@
 // Host-side check of the fused-MLP layout plan (robust-nerf_amd/csrc/mlp_plan.cpp.inc):
 // every parameter's gradient is read by the dW reduction from a slab entry that
-// exactly one dW wave share writes, and every share stays inside its job's grid.
+// exactly one dW wave share writes, and every share stays inside its job's grid; and of
+// the launch descriptors the entry points build from it (the fp32 weight streams, the dW
+// and reduce arguments: the same pure builders, called here without a device).
 //   plan_check pos_freqs dir_freqs n_layers skip_mask use_view_dirs precision
 //   plan_check --sweep     the same checks, in this one process, over the whole config space
 #include <cstdio>
@@ -17,12 +19,108 @@ static int ceil_div(int a, int b) { return (a + b - 1) / b; }
 #include "mlp_plan.cpp.inc"
 using namespace nr;
 
-// The checks of one accepted plan; prints the layout when `say`.  Returns 0 when good.
-static int check_plan(const MlpPlan& p, bool say) {
 #define SAY(...) do { if (say) printf(__VA_ARGS__); } while (0)
+
+// The weight streams as nr_mlp_forward / nr_mlp_backward_dx launch with them (fwd_stream,
+// bwd_stream; their chunk counts do not depend on the precision, so every plan is checked):
+// inside kMaxChunks and the LDS slot, and in fp32, whose images are chunk-major, ending
+// exactly where the next region of `packed` begins.  Returns the number of faults.
+static long check_streams(const MlpPlan& p, bool say, int* fwd_chunks, int* bwd_chunks) {
+    long bad = 0;
+    const int n = p.n_layers;
+    auto one = [&](const char* name, bool built, const StreamDesc& sd, int slot, int slot_max, int64_t end) {
+        if (!built || sd.nq < 1 || sd.nq > kMaxChunks) { ++bad; return; }
+        int64_t kb = 0;
+        for (int q = 0; q < sd.nq; ++q) {
+            bad += sd.ckb[q] < 1 || sd.cadv[q] < sd.ckb[q] || sd.ckb[q] * 1024 > slot;
+            kb += sd.cadv[q];
+        }
+        bad += slot > slot_max || (p.fpb == 4 && sd.base + kb * 1024 != end);
+        SAY("%s stream %d chunks, slot %d bytes\n", name, sd.nq, slot);
+    };
+    StreamDesc sd;
+    const char* why = "";
+    int slot = 0;
+    bool built = fwd_stream(p, &sd, &slot, &why);
+    one("forward", built, sd, slot, kFwdSlotMax, p.lin[n + 1].pk_bwd);
+    *fwd_chunks = sd.nq;
+    built = bwd_stream(p, true, &sd, &slot, &why);
+    one("backward", built, sd, slot, kBwdSlotMax, p.lin[0].vb);
+    *bwd_chunks = sd.nq;
+    built = bwd_stream(p, false, &sd, &slot, &why);
+    one("backward (no input gradients)", built, sd, slot, kBwdSlotMax, p.lin[0].pk_bwd);
+    return bad;
+}
+
+// The dW and reduce launches as nr_mlp_backward_dw / nr_mlp_backward_reduce build them for M
+// samples (dw_args, reduce_args), over buffers at two far-apart integer addresses.  Returns
+// the number of faults.
+static long check_dw_launch(const MlpPlan& p, const MlpSizes& z) {
+    const uintptr_t sv = uintptr_t(1) << 40, ws = uintptr_t(1) << 44;
+    static DwArgs w;
+    static ReduceArgs r;
+    int nwg = 0;
+    size_t lds = 0;
+    const char* why = "";
+    if (!dw_args(p, z, reinterpret_cast<const char*>(sv), reinterpret_cast<char*>(ws), &w, &nwg, &lds, &why)) return 1;
+    long bad = 0;
+    // wg_map: every (job, chunk) pair once, chunk-major
+    int want = 0, min_chunks = z.job_chunks[0], last = -1;
+    for (int j = 0; j < p.n_jobs; ++j) {
+        bad += w.job_chunks[j] != z.job_chunks[j];
+        want += z.job_chunks[j];
+        min_chunks = z.job_chunks[j] < min_chunks ? z.job_chunks[j] : min_chunks;
+    }
+    bad += nwg != want || nwg > kDwMaxWgs || w.njobs != p.n_jobs;
+    for (int i = 0; i < nwg && i < kDwMaxWgs; ++i) {
+        const int j = w.wg_map[i] & 31, c = w.wg_map[i] >> 5;
+        bad += j >= p.n_jobs || c >= z.job_chunks[j] || c * 32 + j <= last;  // increasing: no pair twice
+        last = c * 32 + j;
+    }
+    // the staging ring, the scratch KB, then the list entries of the largest chunk
+    const size_t ring = static_cast<size_t>(w.nstage) * w.stage_bytes + kFragBytes;
+    bad += w.nstage < 2 || w.nstage > NR_DW_NSTAGE || lds > static_cast<size_t>(kDwLdsBytes) || lds < ring;
+    if (w.list_lds != 0)
+        bad += static_cast<size_t>(w.list_lds) < ring || w.list_lds + 4 * ((z.tiles + min_chunks - 1) / min_chunks) > int64_t(lds);
+    // every pointer inside the buffer it was offset from, with what the kernel reads there
+    auto outside = [&](const void* ptr, int64_t bytes, bool in_ws) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(ptr), base = in_ws ? ws : sv;
+        return a < base || a + bytes > base + (in_ws ? z.ws_bytes : z.saved_bytes);
+    };
+    bad += outside(w.slabs, z.max_chunks * p.slab_floats_per_chunk * 4, true) || outside(w.list, z.tiles * 4, true) ||
+           outside(w.count, 4, true);
+    for (int j = 0; j < p.n_jobs; ++j) {
+        const DwJob& jb = p.job[j];
+        // a stage holds the job's blocks of one tile, staged in at most dw_max_pieces pieces per wave
+        const int pieces = (w.job_NBz[j] + w.job_KB[j]) * p.fpb;
+        bad += w.stage_bytes < pieces * kFragBytes || (pieces + kDwWaves - 1) / kDwWaves > dw_max_pieces(p.fpb == 2) ||
+               w.job_NBz[j] != jb.NBz || w.job_KB[j] != jb.KB;
+        for (int s = 0; s < jb.ndz + jb.nin; ++s) {
+            const DwSeg& sg = s < jb.ndz ? jb.dz[s] : jb.in[s - jb.ndz];
+            const int F = sg.is_ws ? p.ws_F[sg.tensor] : p.sv_F[sg.tensor];
+            bad += w.seg_blocks[j][s] != sg.blocks || sg.blocks * 32 != F ||  // the kernel strides a tile by its blocks
+                   outside(w.seg_ptr[j][s], z.tiles_alloc * F * 32 * p.esize, sg.is_ws != 0);
+        }
+        for (int v = 0; v < kDwWaves; ++v) {  // the packed share, field by field
+            const int k = w.job_wave[j][v];
+            if (v >= jb.nwaves) { bad += k != 0; continue; }
+            const DwWave& sh = jb.w[v];
+            bad += (k & 63) != sh.row0 || (k >> 6 & 7) != sh.np || (k >> 9 & 63) != sh.col0 || (k >> 15 & 3) != sh.nq ||
+                   (k >> 17) != sh.bias;
+        }
+    }
+    const int max_rows = reduce_args(p, z, reinterpret_cast<const char*>(ws), nullptr, &r);
+    bad += r.slabs != w.slabs || r.n_red != p.n_red;
+    for (int k = 0; k < p.n_red; ++k) bad += r.rows[k] != p.red[k].rows || r.rows[k] > max_rows;
+    for (int j = 0; j < p.n_jobs; ++j) bad += r.job_chunks[j] != z.job_chunks[j] || r.job_slab[j] != w.job_slab[j];
+    return bad;
+}
+
+// The checks of one accepted plan; prints the layout when `say`.  Returns 0 when good.
+static int check_plan(const MlpPlan& p, bool say, int* fwd_chunks, int* bwd_chunks) {
     if (p.n_jobs > kMaxJobs || p.n_red > kMaxRed) { printf("job or reduce table overrun\n"); return 1; }
-    // the fp32 weight streams of nr_mlp_forward / nr_mlp_backward_dx (with input gradients)
-    if (fwd_stream_chunks(p) > kMaxChunks || bwd_stream_chunks(p) > kMaxChunks) { printf("weight stream overrun\n"); return 1; }
+    const long stream_bad = check_streams(p, say, fwd_chunks, bwd_chunks);
+    SAY("weight streams bad %ld\n", stream_bad);
     // shares write whole 32 x 32 blocks (and a 32-row piece of the bias column, block
     // column KB), so the bookkeeping is per block: writes[job][block row][block column]
     static std::vector<uint8_t> writes[kMaxJobs];
@@ -34,17 +132,12 @@ static int check_plan(const MlpPlan& p, bool say) {
     long dup = 0;
     for (int j = 0; j < p.n_jobs; ++j) {
         const DwJob& jb = p.job[j];
-        if (jb.NBz < 0 || jb.KB < 0 || jb.NBz >= 64 || jb.KB >= 64) { printf("job grid beyond the wave pack\n"); return 1; }
+        if (jb.NBz < 0 || jb.KB < 0) { printf("negative job grid\n"); return 1; }
         writes[j].assign(jb.NBz * (jb.KB + 1), 0);
     }
     for (int j = 0; j < p.n_jobs; ++j) {
         const DwJob& jb = p.job[j];
         SAY("job %d NBz %d KB %d waves %d:", j, jb.NBz, jb.KB, jb.nwaves);
-        // the dW kernel stages at most dw_max_pieces 1-KB pieces per wave and tile
-        if ((jb.NBz + jb.KB) * p.fpb > kDwMaxWaves * dw_max_pieces(p.fpb == 2)) {
-            printf("\nstaging exceeds the per-wave pieces\n");
-            return 1;
-        }
         if (jb.nwaves > kDwMaxWaves || jb.ndz > kMaxJobSeg || jb.nin > kMaxJobSeg) { printf("\njob overrun\n"); return 1; }
         for (int v = 0; v < jb.nwaves; ++v) {
             const DwWave& w = jb.w[v];
@@ -89,8 +182,9 @@ static int check_plan(const MlpPlan& p, bool say) {
         }
     }
     SAY("params %ld (plan %ld) unwritten %ld doubly written %ld\n", n, (long)p.param_count, bad, dup);
-    // dW workgroups per job (make_sizes): one round, every job at least one chunk, the
-    // slab sets cover the largest job; uniform for 16-bit (the pipelined backward's chunks)
+    // dW workgroups per job (make_sizes): every job at least one chunk, the slab sets cover
+    // the largest job; uniform for 16-bit (the pipelined backward's chunks); and the launch
+    // built from them is one round of workgroups with everything in its place
     long wg_bad = 0;
     for (long M : {1L, 5000L, 262144L, 786432L}) {
         const MlpSizes z = make_sizes(p, M);
@@ -103,7 +197,8 @@ static int check_plan(const MlpPlan& p, bool say) {
             wg_bad += z.job_chunks[j] < 1 || (p.fpb == 2 && z.job_chunks[j] != z.chunks);
         }
         SAY(" (sum %d)\n", tot);
-        wg_bad += tot > 256 || mx != z.max_chunks;
+        wg_bad += mx != z.max_chunks;
+        wg_bad += check_dw_launch(p, z);
     }
     SAY("dW workgroup plan bad %ld\n", wg_bad);
     // what the 16-bit input-gradient pass reads of either workspace (din_offsets): equal to the
@@ -150,8 +245,7 @@ static int check_plan(const MlpPlan& p, bool say) {
         din_check(q, f.tiles + kScratchTiles, f.nseg * kSegTiles);
     }
     SAY("input-gradient offsets bad %ld\n", din_bad);
-#undef SAY
-    return bad != 0 || dup != 0 || n != p.param_count || wg_bad != 0 || din_bad != 0;
+    return bad != 0 || dup != 0 || n != p.param_count || stream_bad != 0 || wg_bad != 0 || din_bad != 0;
 }
 
 // pos_freqs 0..11, dir_freqs 0..5, depth 0..17, both view-direction settings, the three
@@ -195,11 +289,12 @@ static int sweep() {
                                 continue;
                             }
                             ++accepted;
-                            if (!valid || check_plan(p, false)) { printf("FAIL %s %d %d %d %u %d %d\n", valid ? "check" : "accepted invalid", L, Ld, n, mask, vd, prec); ++failures; }
+                            int fwd_chunks = 0, bwd_chunks = 0;
+                            if (!valid || check_plan(p, false, &fwd_chunks, &bwd_chunks)) { printf("FAIL %s %d %d %d %u %d %d\n", valid ? "check" : "accepted invalid", L, Ld, n, mask, vd, prec); ++failures; }
                             max_jobs = p.n_jobs > max_jobs ? p.n_jobs : max_jobs;
                             max_red = p.n_red > max_red ? p.n_red : max_red;
-                            max_fwd = fwd_stream_chunks(p) > max_fwd ? fwd_stream_chunks(p) : max_fwd;
-                            max_bwd = bwd_stream_chunks(p) > max_bwd ? bwd_stream_chunks(p) : max_bwd;
+                            max_fwd = fwd_chunks > max_fwd ? fwd_chunks : max_fwd;
+                            max_bwd = bwd_chunks > max_bwd ? bwd_chunks : max_bwd;
                         }
     }
     printf("sweep total %ld accepted %ld refused_valid %ld refused_invalid %ld failures %ld\n", total, accepted,
@@ -215,5 +310,6 @@ int main(int argc, char** argv) {
     if (argc == 7) c = {atoi(argv[1]), atoi(argv[2]), 256, atoi(argv[3]), (uint32_t)atoi(argv[4]), atoi(argv[5]), atoi(argv[6])};
     MlpPlan p; const char* why = "";
     if (!make_plan(&c, &p, &why)) { printf("plan fail %s\n", why); return 1; }
-    return check_plan(p, true);
+    int fwd_chunks, bwd_chunks;
+    return check_plan(p, true, &fwd_chunks, &bwd_chunks);
 }
