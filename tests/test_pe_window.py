@@ -19,9 +19,11 @@ from pathlib import Path
 
 import pytest
 import torch
-import torch.nn as nn
 
 from oracle import refimpl as ref
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from feature_interaction_ref import _cols, _enc_columns, _folded_oracle, windowed_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -33,60 +35,13 @@ def _weights(L, frac=0.34):
     return pe_window_weights(frac * L, L)
 
 
-def _cols(w, dtype=torch.float64):
-    """The per-column scale of an encoder's output: 1 on the 3 raw columns, w_k on the 6 of frequency k."""
-    return torch.tensor([1.0] * 3 + [wk for wk in w for _ in range(6)], dtype=dtype)
-
-
 def _window_of(cfg, frac=0.34):
     return _weights(cfg.pos_freqs, frac), (_weights(cfg.dir_freqs, frac) if cfg.use_view_dirs else None)
 
 
-class _Scaled(nn.Module):
-    """An oracle encoder with its output columns weighted."""
-
-    def __init__(self, enc, cols):
-        super().__init__()
-        self.enc, self.cols = enc, cols
-
-    def forward(self, x):
-        return self.enc(x) * self.cols.to(x.dtype)
-
-
 def _windowed_oracle64(cfg, state, window):
     """oracle.refimpl.NeRF in fp64 with its two encoders' outputs times the column weights."""
-    o = ref.NeRF(cfg).double()
-    o.load_state_dict({k: v.detach().double().cpu() for k, v in state.items()})
-    pos, dir_ = window
-    if pos is not None:
-        o.pos_encoder = _Scaled(o.pos_encoder, _cols(pos))
-    if dir_ is not None:
-        o.dir_encoder = _Scaled(o.dir_encoder, _cols(dir_))
-    return o
-
-
-def _enc_columns(cfg):
-    """(parameter name, first column, encoder) of every weight that reads an encoding."""
-    out = [("pts_linears.0.weight", 0, "pos")]
-    out += [(f"pts_linears.{i + 1}.weight", 0, "pos") for i in sorted(cfg.skips)]
-    if cfg.use_view_dirs:
-        out.append(("dir_linear.weight", cfg.hidden_dim, "dir"))
-    return out
-
-
-def _folded_oracle(cfg, state, window):
-    """An fp32 oracle whose weights carry the window: W * s in fp32 on the encoding columns,
-    which is exactly what the fold converts to the images' precision."""
-    o = ref.NeRF(cfg)
-    o.load_state_dict({k: v.detach().float().cpu() for k, v in state.items()})
-    params = dict(o.named_parameters())
-    with torch.no_grad():
-        for name, c0, which in _enc_columns(cfg):
-            w = window[0] if which == "pos" else window[1]
-            if w is not None:
-                s = _cols(w, torch.float32)
-                params[name][:, c0:c0 + s.numel()] *= s
-    return o
+    return windowed_oracle(cfg, state, window, torch.float64)
 
 
 def _kink_free(model, x, d, eps):
