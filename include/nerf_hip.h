@@ -123,6 +123,50 @@ int nr_rays_from_pixels_intr_bwd(const int64_t* img_idx, const float* pix,
                                  const float* g_rays_d, float* g_poses,
                                  float* g_fxy, void* workspace,
                                  nr_stream_t stream);
+/* ---- A1 / A3 with a learned lens (no reference counterpart; the other half
+ *          of the same future-work bullet).  A lens is six floats
+ *          {fx, fy, cx, cy, k1, k2}, the NeRF-- / SCNeRF form: the radial
+ *          polynomial acts on the ray side, so it is closed form.  For the
+ *          truncated pixel (u, v), every operation fp32 and rounded once:
+ *            xn = (u - cx)/fx,  yn = (v - cy)/fy,  r2 = xn*xn + yn*yn,
+ *            s = 1 + r2*(k1 + k2*r2),  d = (xn*s, -(yn*s), -1),
+ *          then R d, normalised, as everywhere.  k1 == k2 == 0 makes s exactly
+ *          1 and xn*1 == xn, so with cx = W/2, cy = H/2 the rays are those of the
+ *          _intr_ entries (and of the fixed-focal ones when fx == fy) bit for
+ *          bit: all three run one kernel body.
+ * nr_ray_directions_lens: the direction table under that model, from host
+ * numbers (the evaluation path); the same kernel as nr_ray_directions[_xy],
+ * which pass k1 = k2 = 0, so equal to _xy bit for bit at k = 0.             */
+int nr_ray_directions_lens(int H, int W, float fx, float fy, float cx, float cy,
+                           float k1, float k2, float* dirs, nr_stream_t stream);
+/* nr_rays_from_pixels_intr_fwd with lens = six floats in DEVICE memory, read
+ * when the kernel runs (a captured graph sees the current value).  bad_index,
+ * NaN rays for an out-of-range img_idx and B == 0 (null arrays allowed) as
+ * there.                                                                     */
+int nr_rays_from_pixels_lens_fwd(const int64_t* img_idx, const float* pix,
+                                 const float* poses, int n_img, int H, int W,
+                                 const float* lens, int B, float* rays_o,
+                                 float* rays_d, int* bad_index,
+                                 nr_stream_t stream);
+/* Backward of the above: the kernel body of nr_rays_from_pixels_bwd with six
+ * more rows (18 in all) in its reduction.  g_poses exactly as there
+ * (ACCUMULATED, caller zeroes; each row is reduced on its own, so the
+ * fixed-focal bits at the neutral lens).  g_lens (6 floats) is WRITTEN:
+ * dL/d{fx, fy, cx, cy, k1, k2} summed over the batch, exact zeros when
+ * g_rays_d is NULL or B == 0.  Each image's workgroup carries its six sums
+ * through the fixed tree into workspace ((n_img,6) floats,
+ * nr_..._workspace_bytes(n_img) = n_img*6*4, fully overwritten: an image
+ * without rays writes exact zeros, so no initialisation); a second
+ * one-workgroup launch, made for an empty batch too, adds them over the images
+ * in the order of the _intr_ entry's.  No atomics, the same bits from run to
+ * run; rays with an out-of-range img_idx contribute nothing.                 */
+int64_t nr_rays_from_pixels_lens_bwd_workspace_bytes(int n_img);
+int nr_rays_from_pixels_lens_bwd(const int64_t* img_idx, const float* pix,
+                                 const float* poses, int n_img, int H, int W,
+                                 const float* lens, int B, const float* g_rays_o,
+                                 const float* g_rays_d, float* g_poses,
+                                 float* g_lens, void* workspace,
+                                 nr_stream_t stream);
 /* flag[0] = 1 if any idx[i] (i < n) lies outside [0, limit); flag untouched
  * otherwise (caller zeroes it).  Validation for host wrappers that receive
  * indices from a user (the reference raises IndexError on them).            */

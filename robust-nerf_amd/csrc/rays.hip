@@ -11,10 +11,10 @@
 // The library is built with -ffp-contract=off so that each a*b+c rounds twice,
 // exactly as the reference's separate eager torch ops do.
 //
-// One body per computation: the learned-intrinsics entries (nr_*_xy, nr_*_intr_*) and the
-// windowed encoding run the kernels of the fixed-focal / plain entries (the focal pair as an
-// argument or from device memory, the window null or not), and every block reduction is
-// block_sum_rows.  What the header promises to be bit-identical between two entries is so
+// One body per computation: the learned-intrinsics entries (nr_*_xy, nr_*_intr_*, nr_*_lens*)
+// and the windowed encoding run the kernels of the fixed-focal / plain entries (the focal pair
+// as an argument or from device memory, the six-number lens from device memory, the window
+// null or not), and every block reduction is block_sum_rows.  What the header promises to be bit-identical between two entries is so
 // because both run the same code.
 #include <type_traits>
 
@@ -32,14 +32,29 @@ __device__ __forceinline__ float linspace_at(float start, float end, int n, int 
 }
 
 // ---------------------------------------------------------------- A1 -----
+// Radial factor of the lens model (NeRF-- / SCNeRF form, on the ray side, so closed form):
+// s = 1 + r2 (k1 + k2 r2) with r2 = x^2 + y^2 of the pinhole direction.  k1 == k2 == 0 gives
+// exactly 1.0f for any finite r2, and x * 1.0f == x, so a lens without distortion leaves the
+// pinhole direction's bits alone.
+__device__ __forceinline__ float radial_scale(float x, float y, float k1, float k2, float& r2) {
+    r2 = x * x + y * y;
+    return 1.0f + r2 * (k1 + k2 * r2);
+}
+
 // A focal length per axis: the reference has one (nr_ray_directions passes it twice), learned
-// intrinsics have two (nr_ray_directions_xy).
-__global__ void ray_directions_kernel(int H, int W, float fx, float fy, float cx, float cy, float* dirs) {
+// intrinsics have two (nr_ray_directions_xy), a learned lens adds k1, k2 (nr_ray_directions_lens;
+// the other two pass zeros).
+__global__ void ray_directions_kernel(int H, int W, float fx, float fy, float cx, float cy, float k1, float k2,
+                                      float* dirs) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= H * W) return;
     const int j = p / W, i = p % W;  // meshgrid indexing='xy': dirs[j][i]
-    dirs[3 * p + 0] = (static_cast<float>(i) - cx) / fx;
-    dirs[3 * p + 1] = -((static_cast<float>(j) - cy) / fy);
+    const float xn = (static_cast<float>(i) - cx) / fx;
+    const float yn = (static_cast<float>(j) - cy) / fy;
+    float r2;
+    const float s = radial_scale(xn, yn, k1, k2, r2);
+    dirs[3 * p + 0] = xn * s;
+    dirs[3 * p + 1] = -(yn * s);
     dirs[3 * p + 2] = -1.0f;
 }
 
@@ -145,23 +160,39 @@ __global__ void __launch_bounds__(kGrThreads) get_rays_bwd_final_kernel(const fl
 }
 
 // ---------------------------------------------------------------- A3 -----
-// Camera-frame direction of pixel (u,v): the reference gathers it from the
+// Pinhole camera-frame direction of pixel (u,v): the reference gathers it from the
 // precomputed get_ray_directions table with .long() (truncating) indices.
-__device__ __forceinline__ void pixel_dir(const float* pix, int b, int W, int H, float fx, float fy, float& dx,
+__device__ __forceinline__ void pixel_dir(const float* pix, int b, float fx, float fy, float cx, float cy, float& dx,
                                           float& dy) {
     const int u = static_cast<int>(pix[2 * b]);
     const int v = static_cast<int>(pix[2 * b + 1]);
-    dx = (static_cast<float>(u) - static_cast<float>(W) * 0.5f) / fx;
-    dy = -((static_cast<float>(v) - static_cast<float>(H) * 0.5f) / fy);
+    dx = (static_cast<float>(u) - cx) / fx;
+    dy = -((static_cast<float>(v) - cy) / fy);
 }
 
-// The pixel kernels take their focal lengths as Focal = float, the reference's one number as a
-// kernel argument (no memory read), or Focal = const float*, learned intrinsics {fx, fy} in
-// DEVICE memory read when the kernel runs: a captured graph then sees the value of each
-// replay, where an argument would be baked in at capture.  One body serves both, so
-// fx == fy == focal gives the same rays and pose gradients to the bit by construction.
-__device__ __forceinline__ void focal_pair(float focal, float& fx, float& fy) { fx = fy = focal; }
-__device__ __forceinline__ void focal_pair(const float* fxy, float& fx, float& fy) { fx = fxy[0], fy = fxy[1]; }
+// The pixel kernels take their camera as Focal = float, the reference's one number as a
+// kernel argument (no memory read); Focal = const float*, learned intrinsics {fx, fy}; or
+// Focal = LensPtr, a learned lens {fx, fy, cx, cy, k1, k2}.  The last two are in DEVICE memory,
+// read when the kernel runs: a captured graph then sees the value of each replay, where an
+// argument would be baked in at capture.  One body serves all three.  The first two have the
+// principal point at (W/2, H/2) and no distortion step at all, so fx == fy == focal gives the
+// same rays and pose gradients to the bit by construction; the lens at that principal point
+// with k1 == k2 == 0 multiplies by s == 1.0f and gives them too.
+struct LensPtr {
+    const float* p;
+};
+struct Camera {
+    float fx, fy, cx, cy, k1, k2;
+};
+__device__ __forceinline__ Camera camera_of(float focal, int W, int H) {
+    return {focal, focal, static_cast<float>(W) * 0.5f, static_cast<float>(H) * 0.5f, 0.f, 0.f};
+}
+__device__ __forceinline__ Camera camera_of(const float* fxy, int W, int H) {
+    return {fxy[0], fxy[1], static_cast<float>(W) * 0.5f, static_cast<float>(H) * 0.5f, 0.f, 0.f};
+}
+__device__ __forceinline__ Camera camera_of(LensPtr lens, int, int) {
+    return {lens.p[0], lens.p[1], lens.p[2], lens.p[3], lens.p[4], lens.p[5]};
+}
 
 template <typename Focal>
 __global__ void rays_from_pixels_fwd_kernel(const int64_t* img_idx, const float* pix, const float* poses,
@@ -176,9 +207,15 @@ __global__ void rays_from_pixels_fwd_kernel(const int64_t* img_idx, const float*
         return;
     }
     const float* P = poses + 16 * img;
-    float fx, fy, dx, dy;
-    focal_pair(focal, fx, fy);
-    pixel_dir(pix, b, W, H, fx, fy, dx, dy);
+    const Camera cam = camera_of(focal, W, H);
+    float dx, dy;
+    pixel_dir(pix, b, cam.fx, cam.fy, cam.cx, cam.cy, dx, dy);
+    if constexpr (std::is_same<Focal, LensPtr>::value) {
+        float r2;
+        const float s = radial_scale(dx, dy, cam.k1, cam.k2, r2);
+        dx *= s;
+        dy *= s;
+    }
     float x, y, z;
     rotate_normalize(P, dx, dy, -1.0f, x, y, z);
     rd[3 * b] = x;
@@ -198,6 +235,11 @@ __global__ void rays_from_pixels_fwd_kernel(const int64_t* img_idx, const float*
 // own, so the first 12 do not change): the image's focal terms {dL/dfx, dL/dfy}, WRITTEN
 // to focal_part[img] (an image without rays in the batch: an exact 0).  They are gv taken
 // back to the camera frame (g_d = R^T gv) times d(dx)/d(fx) = -dx/fx, d(dy)/d(fy) = -dy/fy.
+// A learned lens carries six such rows {fx, fy, cx, cy, k1, k2} (18 in all) to lens_part[img]:
+// with (px, py) the pinhole direction, d = (px s, py s, -1) and q = g_dx px + g_dy py the
+// cotangent of s, dL/dk1 = q r2, dL/dk2 = q r2^2, and the cotangent of the pinhole direction
+// is g_p = g_d s + 2 p q (k1 + 2 k2 r2); then dL/dfx = g_px (-px/fx) as above,
+// dL/dcx = g_px (-1/fx), dL/dcy = g_py (1/fy) (py = -(v - cy)/fy).
 constexpr int kPoseRedThreads = 256;
 
 template <typename Focal>
@@ -205,12 +247,13 @@ __global__ void __launch_bounds__(kPoseRedThreads)
 rays_from_pixels_bwd_kernel(const int64_t* img_idx, const float* pix, const float* poses, int n_img, int H, int W,
                             Focal focal, int B, const float* g_ro, const float* g_rd, float* g_poses,
                             float* focal_part) {
-    constexpr bool kFocalGrad = std::is_pointer<Focal>::value;
-    constexpr int kRows = kFocalGrad ? 14 : 12;
+    constexpr bool kLens = std::is_same<Focal, LensPtr>::value;
+    constexpr bool kFocalGrad = kLens || std::is_pointer<Focal>::value;
+    constexpr int kCamRows = kLens ? 6 : (kFocalGrad ? 2 : 0);
+    constexpr int kRows = 12 + kCamRows;
     const int img = blockIdx.x;
     const float* P = poses + 16 * static_cast<int64_t>(img);
-    float fx, fy;
-    focal_pair(focal, fx, fy);
+    const Camera cam = camera_of(focal, W, H);
     float acc[kRows];
     for (int e = 0; e < kRows; ++e) acc[e] = 0.f;
     for (int b = threadIdx.x; b < B; b += kPoseRedThreads) {
@@ -218,15 +261,32 @@ rays_from_pixels_bwd_kernel(const int64_t* img_idx, const float* pix, const floa
         for (int r = 0; r < 3; ++r) acc[9 + r] += g_ro[3 * b + r];
         if (!g_rd) continue;
         float d3[3] = {0.f, 0.f, -1.0f}, gv[3];
-        pixel_dir(pix, b, W, H, fx, fy, d3[0], d3[1]);
+        pixel_dir(pix, b, cam.fx, cam.fy, cam.cx, cam.cy, d3[0], d3[1]);
+        const float px = d3[0], py = d3[1];  // the pinhole direction
+        float r2 = 0.f, s = 1.0f;
+        if constexpr (kLens) {
+            s = radial_scale(px, py, cam.k1, cam.k2, r2);
+            d3[0] *= s;
+            d3[1] *= s;
+        }
         dir_cotangent(P, d3, g_rd + 3 * b, gv);
         for (int r = 0; r < 3; ++r)
             for (int k = 0; k < 3; ++k) acc[3 * r + k] += gv[r] * d3[k];
         if constexpr (kFocalGrad) {
-            const float g_dx = (P[0] * gv[0] + P[4] * gv[1]) + P[8] * gv[2];
-            const float g_dy = (P[1] * gv[0] + P[5] * gv[1]) + P[9] * gv[2];
-            acc[12] += g_dx * (-d3[0] / fx);
-            acc[13] += g_dy * (-d3[1] / fy);
+            float g_px = (P[0] * gv[0] + P[4] * gv[1]) + P[8] * gv[2];
+            float g_py = (P[1] * gv[0] + P[5] * gv[1]) + P[9] * gv[2];
+            if constexpr (kLens) {
+                const float q = g_px * px + g_py * py;
+                const float g_r2 = q * (cam.k1 + (2.0f * cam.k2) * r2);
+                acc[16] += q * r2;
+                acc[17] += q * (r2 * r2);
+                g_px = g_px * s + (2.0f * px) * g_r2;
+                g_py = g_py * s + (2.0f * py) * g_r2;
+                acc[14] += g_px * (-1.0f / cam.fx);
+                acc[15] += g_py * (1.0f / cam.fy);
+            }
+            acc[12] += g_px * (-px / cam.fx);
+            acc[13] += g_py * (-py / cam.fy);
         }
     }
     const float t = block_sum_rows<kRows, kPoseRedThreads>(acc);
@@ -234,7 +294,7 @@ rays_from_pixels_bwd_kernel(const int64_t* img_idx, const float* pix, const floa
     if (e < 12)
         g_poses[16 * static_cast<int64_t>(img) + pose_slot(e)] += t;
     else if (e < kRows)
-        focal_part[2 * static_cast<int64_t>(img) + (e - 12)] = t;
+        focal_part[kCamRows * static_cast<int64_t>(img) + (e - 12)] = t;
 }
 
 // Any image index outside [0, n_img) -> flag[0] = 1 (checked by the host wrapper).
@@ -243,17 +303,18 @@ __global__ void check_img_idx_kernel(const int64_t* img_idx, int B, int n_img, i
     if (b < B && (img_idx[b] < 0 || img_idx[b] >= n_img)) flag[0] = 1;
 }
 
-// One workgroup: thread t sums the focal partials of images t, t + 256, ... in that order,
-// then the fixed tree over the threads.  Writes g_fxy[0..1] (n_img == 0: zeros).
+// One workgroup: thread t sums the N-wide camera partials (N = 2 focal, 6 lens) of images
+// t, t + 256, ... in that order, then the fixed tree over the threads.  Writes g_cam[0..N-1]
+// (n_img == 0: zeros).
+template <int N>
 __global__ void __launch_bounds__(kPoseRedThreads)
-focal_grad_final_kernel(const float* focal_part, int n_img, float* g_fxy) {
-    float s[2] = {0.f, 0.f};
-    for (int i = threadIdx.x; i < n_img; i += kPoseRedThreads) {
-        s[0] += focal_part[2 * i];
-        s[1] += focal_part[2 * i + 1];
-    }
-    const float t = block_sum_rows<2, kPoseRedThreads>(s);
-    if (threadIdx.x < 2) g_fxy[threadIdx.x] = t;
+focal_grad_final_kernel(const float* focal_part, int n_img, float* g_cam) {
+    float s[N];
+    for (int e = 0; e < N; ++e) s[e] = 0.f;
+    for (int i = threadIdx.x; i < n_img; i += kPoseRedThreads)
+        for (int e = 0; e < N; ++e) s[e] += focal_part[N * static_cast<int64_t>(i) + e];
+    const float t = block_sum_rows<N, kPoseRedThreads>(s);
+    if (threadIdx.x < N) g_cam[threadIdx.x] = t;
 }
 
 // ---------------------------------------------------------------- A4 -----
@@ -576,7 +637,7 @@ int nr_ray_directions(int H, int W, float focal, float cx, float cy, float* dirs
     NR_REQUIRE(H > 0 && W > 0 && dirs, "nr_ray_directions: bad arguments");
     const int n = H * W;
     hipLaunchKernelGGL(ray_directions_kernel, dim3(ceil_div(n, 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), H, W, focal, focal, cx, cy, dirs);
+                       static_cast<hipStream_t>(stream), H, W, focal, focal, cx, cy, 0.f, 0.f, dirs);
     NR_LAUNCH_CHECK("nr_ray_directions");
     return NR_OK;
 }
@@ -585,8 +646,18 @@ int nr_ray_directions_xy(int H, int W, float fx, float fy, float cx, float cy, f
     NR_REQUIRE(H > 0 && W > 0 && dirs, "nr_ray_directions_xy: bad arguments");
     const int n = H * W;
     hipLaunchKernelGGL(ray_directions_kernel, dim3(ceil_div(n, 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), H, W, fx, fy, cx, cy, dirs);
+                       static_cast<hipStream_t>(stream), H, W, fx, fy, cx, cy, 0.f, 0.f, dirs);
     NR_LAUNCH_CHECK("nr_ray_directions_xy");
+    return NR_OK;
+}
+
+int nr_ray_directions_lens(int H, int W, float fx, float fy, float cx, float cy, float k1, float k2, float* dirs,
+                           nr_stream_t stream) {
+    NR_REQUIRE(H > 0 && W > 0 && dirs, "nr_ray_directions_lens: bad arguments");
+    const int n = H * W;
+    hipLaunchKernelGGL(ray_directions_kernel, dim3(ceil_div(n, 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), H, W, fx, fy, cx, cy, k1, k2, dirs);
+    NR_LAUNCH_CHECK("nr_ray_directions_lens");
     return NR_OK;
 }
 
@@ -673,9 +744,46 @@ int nr_rays_from_pixels_intr_bwd(const int64_t* img_idx, const float* pix, const
         NR_LAUNCH_CHECK("nr_rays_from_pixels_intr_bwd");
     }
     // an empty batch has no partials: the final launch then writes zeros
-    hipLaunchKernelGGL(focal_grad_final_kernel, dim3(1), dim3(kPoseRedThreads), 0, static_cast<hipStream_t>(stream),
-                       focal_part, B > 0 ? n_img : 0, g_fxy);
+    hipLaunchKernelGGL(focal_grad_final_kernel<2>, dim3(1), dim3(kPoseRedThreads), 0,
+                       static_cast<hipStream_t>(stream), focal_part, B > 0 ? n_img : 0, g_fxy);
     NR_LAUNCH_CHECK("nr_rays_from_pixels_intr_bwd");
+    return NR_OK;
+}
+
+int nr_rays_from_pixels_lens_fwd(const int64_t* img_idx, const float* pix, const float* poses, int n_img, int H,
+                                 int W, const float* lens, int B, float* ro, float* rd, int* bad_index,
+                                 nr_stream_t stream) {
+    NR_REQUIRE(lens && B >= 0 && n_img > 0 && (B == 0 || (img_idx && pix && poses && ro && rd)),
+               "nr_rays_from_pixels_lens_fwd: bad arguments");
+    if (B == 0) return NR_OK;
+    hipLaunchKernelGGL(rays_from_pixels_fwd_kernel<LensPtr>, dim3(ceil_div(B, 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), img_idx, pix, poses, n_img, H, W, LensPtr{lens}, B, ro, rd,
+                       bad_index);
+    NR_LAUNCH_CHECK("nr_rays_from_pixels_lens_fwd");
+    return NR_OK;
+}
+
+int64_t nr_rays_from_pixels_lens_bwd_workspace_bytes(int n_img) {
+    return static_cast<int64_t>(n_img > 0 ? n_img : 1) * 6 * sizeof(float);
+}
+
+int nr_rays_from_pixels_lens_bwd(const int64_t* img_idx, const float* pix, const float* poses, int n_img, int H,
+                                 int W, const float* lens, int B, const float* g_ro, const float* g_rd,
+                                 float* g_poses, float* g_lens, void* workspace, nr_stream_t stream) {
+    NR_REQUIRE(lens && g_poses && g_lens && workspace && B >= 0 && n_img > 0 &&
+                   (B == 0 || (img_idx && pix && poses && g_ro)),
+               "nr_rays_from_pixels_lens_bwd: bad arguments");
+    float* lens_part = static_cast<float*>(workspace);
+    if (B > 0) {
+        hipLaunchKernelGGL(rays_from_pixels_bwd_kernel<LensPtr>, dim3(n_img), dim3(kPoseRedThreads), 0,
+                           static_cast<hipStream_t>(stream), img_idx, pix, poses, n_img, H, W, LensPtr{lens}, B, g_ro,
+                           g_rd, g_poses, lens_part);
+        NR_LAUNCH_CHECK("nr_rays_from_pixels_lens_bwd");
+    }
+    // an empty batch has no partials: the final launch then writes zeros
+    hipLaunchKernelGGL(focal_grad_final_kernel<6>, dim3(1), dim3(kPoseRedThreads), 0,
+                       static_cast<hipStream_t>(stream), lens_part, B > 0 ? n_img : 0, g_lens);
+    NR_LAUNCH_CHECK("nr_rays_from_pixels_lens_bwd");
     return NR_OK;
 }
 

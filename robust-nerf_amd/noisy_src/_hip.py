@@ -88,6 +88,11 @@ _SIGNATURES = {
     "nr_rays_from_pixels_intr_bwd_workspace_bytes": (c_i64, [c_i]),
     "nr_rays_from_pixels_intr_bwd": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp]),
+    "nr_ray_directions_lens": (c_i, [c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp]),
+    "nr_rays_from_pixels_lens_fwd": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_i, c_vp, c_vp, c_vp, c_vp]),
+    "nr_rays_from_pixels_lens_bwd_workspace_bytes": (c_i64, [c_i]),
+    "nr_rays_from_pixels_lens_bwd": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp]),
     "nr_se3_poses_fwd": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp]),
     "nr_check_index_range": (c_i, [c_vp, c_i, c_i, c_vp, c_vp]),
     "nr_se3_poses_bwd": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_i, c_vp, c_vp, c_vp]),

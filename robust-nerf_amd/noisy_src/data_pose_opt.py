@@ -80,7 +80,8 @@ class PixelDataset:
         """Reference data_pose_opt.py:83-148.  ``poses`` holds one pose per UNIQUE image of
         the batch, in ascending image order (``poses_all[torch.unique(indices)]``).
         ``fxy`` (optional, (2,) fp32 device tensor): learnable focal lengths (fx, fy) in place
-        of the dataset's ``focal`` (``ops.rays_from_pixels``)."""
+        of the dataset's ``focal``, or (6,): a lens (fx, fy, cx, cy, k1, k2)
+        (``ops.rays_from_pixels``)."""
         uniq, inv = torch.unique(pixel_batch.image_indices, return_inverse=True)
         if poses.shape[0] != uniq.shape[0]:
             raise ValueError(f"get_rays_from_pixels: {poses.shape[0]} poses for {uniq.shape[0]} unique images")
@@ -115,7 +116,8 @@ class PixelSampler:
         the kernel indexes them by image directly (the reference's unique/select/loop
         gives the same rays), and the pose gradient lands on every image in the batch.
         ``fxy`` (optional, (2,) fp32 device tensor): learnable focal lengths (fx, fy) in place
-        of the dataset's ``focal``; they get a gradient too."""
+        of the dataset's ``focal``, or (6,): a lens (fx, fy, cx, cy, k1, k2); they get a
+        gradient too."""
         ds = self.dataset
         return ops.rays_from_pixels(pixel_batch.image_indices, pixel_batch.pixel_coords, poses, ds.H, ds.W,
                                     ds.focal if fxy is None else fxy, validate=not pixel_batch.in_range)

@@ -411,6 +411,11 @@ class PoseTrainer:
     clip group of its own (0.1), with the pose learning rate, LambdaLR and delay; its
     gradient is appended to the pose-gradient all-reduce.  At ``log_scale = 0`` the rays,
     and with them the networks' and poses' updates, are those without it, bit for bit.
+    With a lens (``intrinsics.has_lens``: principal point, radial distortion) the rays come
+    from its ``lens()`` tensor instead, and EACH of its parameters is a clip group of its own
+    (0.1), so that switching one option on does not change another parameter's clip factor;
+    all share the pose learning rate, LambdaLR, delay and all-reduce buffer.  At a neutral
+    lens (centred, k = 0) the first step is again the plain one, bit for bit.
 
     ``distortion_weight``: as in ``Trainer``; the term's gradient reaches the poses through the
     rendering network like the photometric one.  ``loss`` / ``loss_scale``: as in ``Trainer``."""
@@ -466,8 +471,9 @@ class PoseTrainer:
         if self.intrinsics is None:
             rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses)
         else:
-            # (fx, fy) as a device tensor the ray kernels read; detached before the delay, like the poses
-            fxy = self.intrinsics.fxy()
+            # (fx, fy), or the six-number lens, as a device tensor the ray kernels read; detached
+            # before the delay, like the poses
+            fxy = self.intrinsics.lens() if getattr(self.intrinsics, "has_lens", False) else self.intrinsics.fxy()
             rays_o, rays_d = self.pixel_sampler.get_rays_for_batch(pixel_batch, poses,
                                                                    fxy if optimize_poses else fxy.detach())
         target = pixel_batch.target_rgb
@@ -506,7 +512,7 @@ class PoseTrainer:
         self.optimizer_nerf.step(clip_groups=groups)
         self.scheduler_nerf.step()
         if optimize_poses:
-            groups = [(self.poses, 0.1)] + ([(self.focal, 0.1)] if self.focal else [])
+            groups = [(self.poses, 0.1)] + [([p], 0.1) for p in self.focal]  # one group per camera parameter
             self.optimizer_poses.step(clip_groups=groups)
             self.scheduler_poses.step()
         metrics["loss"] = loss.detach()
@@ -527,8 +533,9 @@ class PoseRefiner:
     must use the small-angle Jacobian (``fixed_small_angle=True``): refinement starts at
     w = 0, where the reference's ``theta < 1e-6`` rule gives a rotation gradient of
     exactly zero.  ``lr_decay`` (optional): the LambdaLR of the training loops.
-    ``fxy`` (optional, (2,) fp32 device tensor): fixed focal lengths (fx, fy), e.g. those a
-    checkpoint learned, in place of the dataset's; the refiner does not learn intrinsics.
+    ``fxy`` (optional, (2,) or (6,) fp32 device tensor): fixed focal lengths (fx, fy) or a
+    fixed lens (fx, fy, cx, cy, k1, k2), e.g. those a checkpoint learned, in place of the
+    dataset's; the refiner does not learn intrinsics.
     ``loss`` / ``loss_scale``: the photometric loss, as in ``Trainer``."""
 
     def __init__(self, model_coarse, model_fine, camera_params, pixel_sampler, render_config,

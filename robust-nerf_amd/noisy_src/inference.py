@@ -81,12 +81,15 @@ def load_checkpoint(checkpoint_path: Path, device: str = "cuda", precision: Opti
 def intrinsics_fxy(ckpt: dict):
     """(fx, fy) a checkpoint learned (its ``intrinsics`` entry, written by ``train_pose_opt
     --learn_focal``: focal_init * exp(log_scale) in fp32, as the training step computes it),
-    or None for a checkpoint without the entry, which renders with the dataset's focal length."""
+    or None for a checkpoint without the entry, which renders with the dataset's focal length.
+    A checkpoint with a lens (``--learn_principal``, ``--learn_distortion``, ``--lens_init``)
+    gives its six numbers (fx, fy, cx, cy, k1, k2) instead; everything here that takes ``fxy``
+    takes either."""
     state = ckpt.get("intrinsics")
     if state is None:
         return None
     from .train_pose_opt import CameraIntrinsics
-    return CameraIntrinsics.from_state_dict({k: v.detach().cpu() for k, v in state.items()}).fxy_values()
+    return CameraIntrinsics.from_state_dict({k: v.detach().cpu() for k, v in state.items()}).camera_values()
 
 
 def _render(renderer, pose, H, W, focal, chunk_size, fxy):
@@ -569,6 +572,8 @@ def main(argv=None) -> None:
         fxy = checkpoint_intrinsics(a.checkpoint)
         if fxy is not None:
             log(f"Learned focal lengths: fx {fxy[0]:.4f}, fy {fxy[1]:.4f} (used in place of the dataset's)")
+            if len(fxy) == 6:
+                log(f"Learned lens: cx {fxy[2]:.4f}, cy {fxy[3]:.4f}, k1 {fxy[4]:.6f}, k2 {fxy[5]:.6f}")
         scene = a.scene or config.get("data", {}).get("scene_name", "lego")
         log(f"Scene: {scene}")
         if a.output_dir is None:

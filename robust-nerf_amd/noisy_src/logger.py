@@ -36,6 +36,12 @@ class TrainingMetrics:
     # learned intrinsics only (train_pose_opt --learn_focal): mean |f / f_dataset - 1| in per
     # cent; None leaves the reference's columns as they are
     focal_error_pct: Optional[float] = None
+    # a learned or held lens only (--learn_principal, --learn_distortion, --lens_init): the
+    # principal point in pixels and the radial terms; None adds no column
+    lens_cx: Optional[float] = None
+    lens_cy: Optional[float] = None
+    lens_k1: Optional[float] = None
+    lens_k2: Optional[float] = None
 
     def to_dict(self) -> Dict[str, Any]:
         return {k: v for k, v in asdict(self).items() if v is not None}

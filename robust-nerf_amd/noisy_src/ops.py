@@ -56,6 +56,19 @@ def ray_directions_xy(H: int, W: int, fx: float, fy: float, cx: float, cy: float
     return out
 
 
+def ray_directions_lens(H: int, W: int, fx: float, fy: float, cx: float, cy: float, k1: float, k2: float,
+                        device) -> torch.Tensor:
+    """``ray_directions_xy`` under the lens model (learned lens, the evaluation path): with
+    xn = (i - cx) / fx, yn = (j - cy) / fy, r2 = xn^2 + yn^2 and s = 1 + r2 (k1 + k2 r2),
+    (xn s, -(yn s), -1); with k1 == k2 == 0 the same bits as ``ray_directions_xy``."""
+    out = torch.empty(H, W, 3, device=device, dtype=_f32)
+    if not out.is_cuda:
+        _check(out)
+    call("nr_ray_directions_lens", H, W, float(fx), float(fy), float(cx), float(cy), float(k1), float(k2), ptr(out),
+         _stream())
+    return out
+
+
 class _GetRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, directions, c2w):
@@ -461,10 +474,10 @@ def composite_loss(rgb, sigma, z_vals, rays_d, target, kind, c, noise=None, whit
 
 # ---------------------------------------------------------------- A3 / A4 ----
 class _RaysFromPixels(torch.autograd.Function):
-    """``focal``: a Python number, a kernel argument; or the focal lengths (fx, fy) in device
-    memory, read when the kernels run (so a captured graph follows a focal length that changes
-    every step), with a gradient for them beside the poses'.  Which of the two only picks the
-    entry point."""
+    """``focal``: a Python number, a kernel argument; or the focal lengths (fx, fy), or the lens
+    (fx, fy, cx, cy, k1, k2), in device memory, read when the kernels run (so a captured graph
+    follows a camera that changes every step), with a gradient for them beside the poses'.
+    Which of the three only picks the entry point."""
 
     @staticmethod
     def forward(ctx, img_idx, pix, poses, H, W, focal, validate):
@@ -475,7 +488,8 @@ class _RaysFromPixels(torch.autograd.Function):
         rd = torch.empty(B, 3, device=px.device, dtype=_f32)
         flag = torch.zeros(1, device=px.device, dtype=torch.int32) if validate else None
         if isinstance(focal, torch.Tensor):
-            entry, fxy, focal = "nr_rays_from_pixels_intr_fwd", focal, ptr(focal)
+            kind = "lens" if focal.numel() == 6 else "intr"
+            entry, fxy, focal = f"nr_rays_from_pixels_{kind}_fwd", focal, ptr(focal)
         else:
             entry, fxy, focal = "nr_rays_from_pixels_fwd", None, float(focal)
         call(entry, ptr(img), ptr(px), ptr(ps), ps.shape[0], H, W, focal, B, ptr(ro), ptr(rd), ptr(flag), _stream())
@@ -497,10 +511,11 @@ class _RaysFromPixels(torch.autograd.Function):
             call("nr_rays_from_pixels_bwd", ptr(img), ptr(px), ptr(ps), n_img, H, W, focal, B, ptr(_c(g_ro)),
                  ptr(_c(g_rd)), ptr(g_poses), _stream())
         else:
-            g_fxy = torch.empty(2, device=px.device, dtype=_f32)  # written, not accumulated
-            ws = torch.empty(int(_hip.load().nr_rays_from_pixels_intr_bwd_workspace_bytes(n_img)), device=px.device,
-                             dtype=torch.uint8)
-            call("nr_rays_from_pixels_intr_bwd", ptr(img), ptr(px), ptr(ps), n_img, H, W, ptr(fxy), B, ptr(_c(g_ro)),
+            kind = "lens" if fxy.numel() == 6 else "intr"
+            g_fxy = torch.empty(fxy.numel(), device=px.device, dtype=_f32)  # written, not accumulated
+            ws_bytes = getattr(_hip.load(), f"nr_rays_from_pixels_{kind}_bwd_workspace_bytes")(n_img)
+            ws = torch.empty(int(ws_bytes), device=px.device, dtype=torch.uint8)
+            call(f"nr_rays_from_pixels_{kind}_bwd", ptr(img), ptr(px), ptr(ps), n_img, H, W, ptr(fxy), B, ptr(_c(g_ro)),
                  ptr(_c(g_rd)), ptr(g_poses), ptr(g_fxy), ptr(ws), _stream())
         return (None, None, g_poses if ctx.needs_input_grad[2] else None, None, None,
                 g_fxy if ctx.needs_input_grad[5] else None, None)
@@ -523,12 +538,15 @@ def rays_from_pixels(img_idx, pix, poses, H, W, focal, validate: bool = False):
     out-of-range rays come out NaN and get no pose gradient.
     ``focal``: a Python number (both axes, no gradient), or a contiguous (2,) fp32 device
     tensor (fx, fy) that the kernels read from device memory and that gets a gradient
-    (learned intrinsics; with fx == fy the same rays and pose gradients bit for bit)."""
+    (learned intrinsics; with fx == fy the same rays and pose gradients bit for bit), or a
+    contiguous (6,) one (fx, fy, cx, cy, k1, k2), the learned lens (``ray_directions_lens``'s
+    model; at cx = W/2, cy = H/2, k1 = k2 = 0 the (2,) form's bits)."""
     _check(img_idx, pix, poses)
     if isinstance(focal, torch.Tensor):
         _check(focal)
-        if focal.shape != (2,) or focal.dtype != _f32 or focal.device != poses.device or not focal.is_contiguous():
-            raise ValueError(f"rays_from_pixels: a tensor focal must be contiguous fp32 (fx, fy) on {poses.device}, "
+        if focal.shape not in ((2,), (6,)) or focal.dtype != _f32 or focal.device != poses.device or not focal.is_contiguous():
+            raise ValueError(f"rays_from_pixels: a tensor focal must be contiguous fp32 (fx, fy) or "
+                             f"(fx, fy, cx, cy, k1, k2) on {poses.device}, "
                              f"got {tuple(focal.shape)} {focal.dtype} on {focal.device}")
     return _RaysFromPixels.apply(img_idx, pix, poses, H, W, focal, bool(validate))
 

@@ -153,6 +153,33 @@ def focal_errors(record) -> Dict[str, object]:
             "optimized_focal_error_pct_mean_abs": float(np.mean(np.abs(e1)))}
 
 
+LENS_KEYS = ("initial_lens", "optimized_lens", "ground_truth_lens")
+LENS_NAMES = ("fx", "fy", "cx", "cy", "k1", "k2")
+
+
+def lens_errors(record) -> Dict[str, object]:
+    """The lens report of a ``final_poses.pt`` written with a lens option (the three ``*_lens``
+    entries, (fx, fy, cx, cy, k1, k2) each): the values, and for cx, cy (pixels), k1, k2 the
+    differences against the ground truth, initial and optimised.  {} for a record without the
+    entries.  The focal pair has its own report (``focal_errors``).  These numbers stand beside
+    the pose errors and are not folded into them: k1 couples with the focal length (both scale
+    the image about its centre, differently only in r^2) and a principal-point shift with a
+    small rotation of every camera (both move the image sideways, differently only at second
+    order), so an error in one is partly an error in the other, and neither is a gauge freedom
+    the Sim(3) alignment could remove."""
+    if not all(k in record for k in LENS_KEYS):
+        return {}
+    init, opt, gt = (torch.as_tensor(record[k], dtype=torch.float64).reshape(-1) for k in LENS_KEYS)
+    if any(t.numel() != 6 for t in (init, opt, gt)):
+        raise ValueError("pose_eval: the *_lens entries must hold six numbers (fx, fy, cx, cy, k1, k2)")
+    out: Dict[str, object] = {"initial_lens": init.tolist(), "optimized_lens": opt.tolist(),
+                              "ground_truth_lens": gt.tolist()}
+    for e, name in enumerate(LENS_NAMES[2:], start=2):
+        out[f"initial_{name}_error"] = float(init[e] - gt[e])
+        out[f"optimized_{name}_error"] = float(opt[e] - gt[e])
+    return out
+
+
 def main(argv=None) -> None:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m noisy_src.pose_eval",
@@ -168,6 +195,9 @@ def main(argv=None) -> None:
     focal = focal_errors(d)
     if focal:
         res["focal"] = focal
+    lens = lens_errors(d)
+    if lens:
+        res["lens"] = lens
     out = a.out if a.out is not None else a.final_poses.parent / "aligned_pose_errors.json"
     out.write_text(json.dumps(res, indent=2))
     print(f"aligned: rot {res['rotation_error_mean']:.4f} deg, trans {res['translation_error_mean']:.5f} "
@@ -176,6 +206,10 @@ def main(argv=None) -> None:
     if focal:
         print(f"focal error: {focal['initial_focal_error_pct_mean_abs']:.3f} % -> "
               f"{focal['optimized_focal_error_pct_mean_abs']:.3f} % (mean |f / f_gt - 1| over fx, fy)")
+    if lens:
+        print("lens error (initial -> optimised, not part of the pose errors): " + "; ".join(
+            f"{n} {lens[f'initial_{n}_error']:+.5f} -> {lens[f'optimized_{n}_error']:+.5f}" for n in LENS_NAMES[2:])
+            + " (cx, cy in pixels)")
 
 
 if __name__ == "__main__":

@@ -127,6 +127,10 @@ def slice_for_rank(n: int, rank: int, world: int, *tensors):
     return sl, tuple(None if t is None else t[sl] for t in tensors)
 
 
+# TrainingMetrics' columns for a lens, pushed as extra scalars by train_pose_opt
+LENS_COLUMNS = ("lens_cx", "lens_cy", "lens_k1", "lens_k2")
+
+
 class IterationLog:
     """One row of train_metrics.csv and, every ``log_every``, one console line per
     iteration, from scalars read back one iteration late (``engine.LaggedScalars``: no
@@ -180,7 +184,8 @@ class IterationLog:
         self.logger.log_training(TrainingMetrics(iteration=it, loss=vm["loss"], loss_coarse=vm["loss_coarse"],
                                                  loss_fine=vm.get("loss_fine"), psnr=psnr, learning_rate=lr,
                                                  time_per_iter=batch_time, rays_per_sec=rays_per_sec,
-                                                 focal_error_pct=vm.get("focal_error_pct")))
+                                                 focal_error_pct=vm.get("focal_error_pct"),
+                                                 **{k: vm[k] for k in LENS_COLUMNS if k in vm}))
         if it % self.log_every == 0:
             self.log(f"[{it:7d}/{self.num_iterations}] loss: {vm['loss']:.5f} | psnr: {psnr:.2f} | "
                      f"{self.line(vm, lr, rays_per_sec, meta)} | time: {self.minutes():.1f}min")

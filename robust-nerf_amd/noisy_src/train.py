@@ -90,12 +90,16 @@ def train_step(renderer: NeRFRenderer, optimizer: torch.optim.Optimizer, batch: 
 def render_image(renderer: NeRFRenderer, pose: torch.Tensor, H: int, W: int, focal: float,
                  chunk_size: int = 1024 * 4, fxy=None) -> Dict[str, torch.Tensor]:
     """Reference train.py:122-160: every pixel of one view, deterministic (is_train=False).
-    ``fxy`` (optional): focal lengths (fx, fy) learned with the poses, in place of ``focal``."""
+    ``fxy`` (optional): focal lengths (fx, fy) learned with the poses, in place of ``focal``;
+    or six numbers, a learned lens (fx, fy, cx, cy, k1, k2) (``ops.ray_directions_lens``)."""
     if fxy is None:
         dirs = get_ray_directions(H, W, focal, device=pose.device)
-    else:
-        from . import ops
+    elif len(fxy) == 2:
         dirs = ops.ray_directions_xy(H, W, fxy[0], fxy[1], W / 2.0, H / 2.0, pose.device)
+    elif len(fxy) == 6:
+        dirs = ops.ray_directions_lens(H, W, *fxy, pose.device)
+    else:
+        raise ValueError(f"render_image: fxy must be (fx, fy) or (fx, fy, cx, cy, k1, k2), got {fxy!r}")
     rays_o, rays_d = get_rays(dirs, pose.detach().contiguous())
     out = renderer(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), chunk_size=chunk_size, is_train=False)
     key = "fine" if "rgb_fine" in out else "coarse"

@@ -34,6 +34,12 @@ Joint NeRF + camera-pose training step — drop-in for ShawnnnLiu/Robust-NeRF
   future-work item): ``CameraIntrinsics`` holds a log scale on the dataset's focal length,
   the ray kernels read (fx, fy) from device memory (``nr_rays_from_pixels_intr_fwd/bwd``), so
   the graphs follow it, and it shares the pose Adam, schedule and delay.
+* ``learn_principal`` / ``learn_distortion`` / ``lens_init`` (``--learn_principal``,
+  ``--learn_distortion``, ``--lens_init K1 K2``) learn the rest of the lens the same way: the
+  principal point and two radial terms of the NeRF-- / SCNeRF ray-side model, six numbers
+  that the ray kernels read from device memory (``nr_rays_from_pixels_lens_fwd/bwd``), each
+  parameter a clip group of its own; ``lens_init`` alone holds a known calibration
+  (DESIGN.md §4c-2).
 """
 
 from __future__ import annotations
@@ -59,7 +65,7 @@ from .model import NeRF
 from .noise import NoiseConfig, add_noise_to_poses, compute_pose_error
 from .optim import FusedAdam, clip_grad_norm_
 from .rendering import NeRFRenderer, render_rays
-from .run import (IterationLog, add_common_args, base_checkpoint, create_nerf_for, draw_randoms, due,  # noqa: F401
+from .run import (LENS_COLUMNS, IterationLog, add_common_args, base_checkpoint, create_nerf_for, draw_randoms, due,  # noqa: F401
                   evaluate_views, loss_line, open_run, run_cli, set_seed, slice_for_rank, write_checkpoint,
                   write_experiment_config)
 from .train import render_image
@@ -155,35 +161,121 @@ class CameraIntrinsics(nn.Module):
     tensor (fx, fy) that the ray kernels read from device memory.  At zero it is
     ``focal_init`` exactly, so the first step's rays are those of the fixed focal length.
     The log makes one learning rate mean the same at every focal length: a step of 1e-4
-    changes it by 0.01 %.  ``focal_init``: a number, or a pair (fx, fy)."""
+    changes it by 0.01 %.  ``focal_init``: a number, or a pair (fx, fy).
+
+    The lens (keyword options) adds the principal point and two radial terms,
+    the NeRF-- / SCNeRF model ``ops.ray_directions_lens`` states.  The module has a lens when
+    ``learn_principal`` or ``learn_distortion`` is set or ``lens_init`` is not (0, 0); it then
+    needs ``image_size=(W, H)``, and ``lens()`` is the (6,) device tensor
+    (fx, fy, cx, cy, k1, k2) the ray kernels read:
+
+    * ``principal`` (2,), zero-initialised, registered with ``learn_principal``:
+      ``cx = W/2 + focal_init_x * principal[0]``, ``cy`` alike.  In units of the focal length
+      for the reason ``log_scale`` is a log: a step of 1e-4 means the same at 50 and at
+      1,100 pixels.  Without it the principal point is (W/2, H/2).
+    * ``radial`` (2,) = (k1, k2), initialised to ``lens_init``, registered with
+      ``learn_distortion``.  Without it a non-zero ``lens_init`` is HELD: a known calibration.
+
+    What is held is a buffer named ``<name>_held`` in place of the parameter ``<name>``:
+    ``learn_focal=False`` keeps the focal length at ``focal_init`` as ``log_scale_held``, and
+    a held calibration is ``radial_held``.  A buffer is no parameter, so no optimizer ever
+    sees it and a held value cannot move; and the state dict's keys alone say which options
+    were on (``from_state_dict``).  A module built without the keyword options is the one
+    described in the first paragraph: parameters ``["log_scale"]``, state-dict keys
+    ``["focal_init", "log_scale"]``."""
 
     MODES = ("shared", "xy")
 
-    def __init__(self, focal_init, mode: str = "shared"):
+    def __init__(self, focal_init, mode: str = "shared", *, learn_focal: bool = True, learn_principal: bool = False,
+                 learn_distortion: bool = False, lens_init=(0.0, 0.0), image_size=None):
         super().__init__()
         if mode not in self.MODES:
             raise ValueError(f"CameraIntrinsics: mode must be one of {self.MODES}, not {mode!r}")
         f = torch.as_tensor(focal_init, dtype=torch.float32).reshape(-1)
         if f.numel() not in (1, 2) or not bool((f > 0).all()):
             raise ValueError(f"CameraIntrinsics: focal_init must be one or two positive numbers, got {focal_init!r}")
+        k = torch.as_tensor(lens_init, dtype=torch.float32).reshape(-1)
+        if k.numel() != 2 or not bool(torch.isfinite(k).all()):
+            raise ValueError(f"CameraIntrinsics: lens_init must be two finite numbers (k1, k2), got {lens_init!r}")
         self.mode = mode
+        self.has_lens = bool(learn_principal or learn_distortion or bool((k != 0).any()))
+        if not learn_focal and not self.has_lens:
+            raise ValueError("CameraIntrinsics: learn_focal=False needs learn_principal, learn_distortion or a "
+                             "non-zero lens_init (there would be nothing to learn or to hold)")
         self.register_buffer("focal_init", f.expand(2).clone())
-        self.log_scale = nn.Parameter(torch.zeros(1 if mode == "shared" else 2))
+        log_scale = torch.zeros(1 if mode == "shared" else 2)
+        if learn_focal:
+            self.log_scale = nn.Parameter(log_scale)
+        else:
+            self.register_buffer("log_scale_held", log_scale)
+        if not self.has_lens:
+            return
+        wh = torch.as_tensor(image_size if image_size is not None else (), dtype=torch.float32).reshape(-1)
+        if wh.numel() != 2 or not bool((wh > 0).all()):
+            raise ValueError(f"CameraIntrinsics: a lens needs image_size=(W, H), two positive numbers, "
+                             f"got {image_size!r}")
+        self.register_buffer("image_size", wh.clone())
+        if learn_principal:
+            self.principal = nn.Parameter(torch.zeros(2))
+        if learn_distortion:
+            self.radial = nn.Parameter(k.clone())
+        elif bool((k != 0).any()):
+            self.register_buffer("radial_held", k.clone())
 
     @classmethod
     def from_state_dict(cls, state) -> "CameraIntrinsics":
-        """The module a checkpoint's ``intrinsics`` entry was saved from (on the CPU)."""
-        out = cls(state["focal_init"], "shared" if state["log_scale"].numel() == 1 else "xy")
+        """The module a checkpoint's ``intrinsics`` entry was saved from (on the CPU).  The keys
+        say how it was built: ``log_scale`` or ``log_scale_held``, ``principal``, ``radial`` or
+        ``radial_held``, and ``image_size`` with any of the lens ones."""
+        learn_focal = "log_scale" in state
+        scale = state["log_scale" if learn_focal else "log_scale_held"]
+        radial = state.get("radial", state.get("radial_held"))
+        size = state.get("image_size")
+        out = cls(state["focal_init"], "shared" if scale.numel() == 1 else "xy", learn_focal=learn_focal,
+                  learn_principal="principal" in state, learn_distortion="radial" in state,
+                  lens_init=(0.0, 0.0) if radial is None else radial.tolist(),
+                  image_size=None if size is None else size.tolist())
         out.load_state_dict(state)
         return out
 
+    def _log_scale(self) -> torch.Tensor:
+        return self.log_scale if hasattr(self, "log_scale") else self.log_scale_held
+
     def fxy(self) -> torch.Tensor:
-        return self.focal_init * torch.exp(self.log_scale)
+        return self.focal_init * torch.exp(self._log_scale())
 
     def fxy_values(self) -> Tuple[float, float]:
         """(fx, fy) as Python floats (one host read; for renders and reports, not the step)."""
         fx, fy = self.fxy().detach().cpu().tolist()
         return fx, fy
+
+    def lens(self) -> torch.Tensor:
+        """(fx, fy, cx, cy, k1, k2) as a (6,) device tensor, from torch ops (a captured graph
+        holds them in front of the ray kernel, as it does ``fxy()``'s).  With every lens
+        parameter at zero it is {fx, fy, W/2, H/2, 0, 0} exactly."""
+        if not self.has_lens:
+            raise ValueError("CameraIntrinsics.lens: built without a lens (learn_principal, learn_distortion, "
+                             "lens_init); use fxy()")
+        centre = self.image_size * 0.5
+        if hasattr(self, "principal"):
+            centre = centre + self.focal_init * self.principal
+        radial = getattr(self, "radial", None)
+        if radial is None:
+            radial = getattr(self, "radial_held", None)
+        if radial is None:
+            radial = torch.zeros_like(centre)
+        return torch.cat([self.fxy(), centre, radial])
+
+    def lens_values(self) -> Tuple[float, float, float, float, float, float]:
+        """(fx, fy, cx, cy, k1, k2) as Python floats (one host read, like ``fxy_values``)."""
+        return tuple(self.lens().detach().cpu().tolist())
+
+    def camera(self) -> torch.Tensor:
+        """What the ray kernels read: ``lens()`` with a lens, ``fxy()`` without."""
+        return self.lens() if self.has_lens else self.fxy()
+
+    def camera_values(self) -> Tuple[float, ...]:
+        return self.lens_values() if self.has_lens else self.fxy_values()
 
     def focal_error_pct(self, reference_focal: float) -> torch.Tensor:
         """mean over the axes of |f / reference - 1| in per cent (a device scalar, no sync)."""
@@ -320,7 +412,9 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
                                  log=print, graph: bool = False, c2f: Optional[Tuple[float, float]] = None,
                                  fixed_small_angle: bool = False, learn_focal: Optional[str] = None,
                                  focal_init_scale: float = 1.0, distortion_weight: float = 0.0,
-                                 loss: str = "mse", loss_scale: float = 0.1) -> Dict[str, object]:
+                                 loss: str = "mse", loss_scale: float = 0.1, learn_principal: bool = False,
+                                 learn_distortion: bool = False,
+                                 lens_init: Tuple[float, float] = (0.0, 0.0)) -> Dict[str, object]:
     """Reference train_pose_opt.py:613-1054 (same arguments, outputs and files).
     ``train_data`` / ``val_data`` (optional) replace the on-disk scene; ``process_group``
     makes it data parallel; ``experiment_name`` pins the generated run name (all ranks).
@@ -339,6 +433,15 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     use the learned value, the log and train_metrics.csv report its error in per cent
     against the dataset's, checkpoints gain ``intrinsics`` and final_poses.pt the three
     ``*_focal`` entries.  None (the default) is the reference's fixed focal length.
+    ``learn_principal`` / ``learn_distortion`` (``--learn_principal``, ``--learn_distortion``)
+    learn the principal point and the radial terms (k1, k2) of ``CameraIntrinsics``' lens the
+    same way, each a clip group of its own; ``lens_init`` (``--lens_init K1 K2``) is where
+    (k1, k2) start, or, without ``learn_distortion``, a known calibration that is held.
+    Without ``learn_focal`` the focal length is then held at the dataset's (times
+    ``focal_init_scale``).  Validation renders use the lens, train_metrics.csv gains
+    ``lens_cx, lens_cy, lens_k1, lens_k2`` and final_poses.pt the three ``*_lens`` entries
+    (six numbers each; the ground truth is the dataset's centred pinhole).  With none of the
+    three nothing changes.
     ``distortion_weight`` > 0 (``--distortion_weight``) adds that multiple of the distortion
     loss on the rendering network's ray weights (``engine.PoseTrainer``); its value goes to
     the console line only.
@@ -376,10 +479,19 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
     camera_params = CameraPoseParameters(initial_poses, learn_rotation, learn_translation,
                                          fixed_small_angle=fixed_small_angle).to(device)
     intrinsics = None
-    if learn_focal is not None:
+    lens_init = tuple(float(k) for k in lens_init)
+    with_lens = bool(learn_principal or learn_distortion or any(k != 0 for k in lens_init))
+    if learn_focal is not None or with_lens:
         if not focal_init_scale > 0:
             raise ValueError(f"focal_init_scale must be positive, got {focal_init_scale}")
-        intrinsics = CameraIntrinsics(train_data.focal * focal_init_scale, learn_focal).to(device)
+        if not with_lens:
+            intrinsics = CameraIntrinsics(train_data.focal * focal_init_scale, learn_focal).to(device)
+        else:
+            intrinsics = CameraIntrinsics(train_data.focal * focal_init_scale, learn_focal or "shared",
+                                          learn_focal=learn_focal is not None, learn_principal=learn_principal,
+                                          learn_distortion=learn_distortion, lens_init=lens_init,
+                                          image_size=(train_data.W, train_data.H)).to(device)
+    initial_lens = intrinsics.lens().detach().cpu() if with_lens else None
     gt_focal = float(train_data.focal)
     model_coarse, model_fine = create_nerf_for(config, device, logger)
     _, pixel_sampler = create_pixel_dataset(train_data)
@@ -396,8 +508,11 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
             extra["c2f"] = list(c2f)
         if fixed_small_angle:
             extra["fixed_small_angle"] = True
-        if intrinsics is not None:
+        if intrinsics is not None and learn_focal is not None:
             extra["learn_focal"] = {"mode": learn_focal, "focal_init_scale": focal_init_scale}
+        if with_lens:
+            extra["lens"] = {"learn_principal": learn_principal, "learn_distortion": learn_distortion,
+                             "lens_init": list(lens_init), "focal_init_scale": focal_init_scale}
         extra["distortion_weight"] = distortion_weight
         extra["loss"], extra["loss_scale"] = loss, loss_scale
         write_experiment_config(output_dir, config, exp_name, world, noise_config, extra=extra, after_name={
@@ -410,12 +525,25 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
 
     def line(vm, lr, rays_per_sec, optimizing):
         focal = f" | focal err: {vm['focal_error_pct']:.3f}%" if "focal_error_pct" in vm else ""
+        if "lens_k1" in vm:
+            focal += (f" | lens: c ({vm['lens_cx']:.3f}, {vm['lens_cy']:.3f}) k ({vm['lens_k1']:.5f}, "
+                      f"{vm['lens_k2']:.5f})")
         if "loss_distortion" in vm:
             focal += f" | distortion: {vm['loss_distortion']:.5f}"
         return f"{loss_line(loss, loss_scale)}lr: {lr:.2e} | poses: {'optimizing' if optimizing else 'frozen'}{focal}"
 
-    def learned_fxy():
-        return intrinsics.fxy_values() if intrinsics is not None else None
+    def learned_fxy():  # two numbers, or the six of a lens
+        return intrinsics.camera_values() if intrinsics is not None else None
+
+    def extra_scalars():
+        """Device scalars for the iteration log: the focal error, and the lens's last four."""
+        if intrinsics is None:
+            return None
+        out = {"focal_error_pct": intrinsics.focal_error_pct(gt_focal)}
+        if with_lens:
+            with torch.no_grad():
+                out.update(zip(LENS_COLUMNS, intrinsics.lens()[2:].unbind()))
+        return out
 
     def checkpoint(iteration, pe, **kw):
         save_checkpoint_with_poses(output_dir, iteration, model_coarse, model_fine, camera_params, optimizer_nerf,
@@ -442,8 +570,7 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
         else:
             m = trainer.step(*args, iteration=iteration)
         # the focal error is a device scalar like the losses: read one iteration late
-        ilog.push(iteration, m, optimizer_nerf.param_groups[0]["lr"],
-                  {"focal_error_pct": intrinsics.focal_error_pct(gt_focal)} if intrinsics is not None else None, now)
+        ilog.push(iteration, m, optimizer_nerf.param_groups[0]["lr"], extra_scalars(), now)
         what = due(iteration, config.train.val_every, config.train.save_every) if logger is not None else None
         if what:
             ilog.flush()
@@ -486,6 +613,10 @@ def train_with_pose_optimization(config: NeRFConfig, noise_config: Optional[Nois
             record.update(initial_focal=intrinsics.focal_init.detach().cpu().clone(),
                           optimized_focal=intrinsics.fxy().detach().cpu(),
                           ground_truth_focal=torch.full((2,), gt_focal, dtype=torch.float32))
+        if with_lens:  # (fx, fy, cx, cy, k1, k2) each, for pose_eval's lens report
+            record.update(initial_lens=initial_lens, optimized_lens=intrinsics.lens().detach().cpu(),
+                          ground_truth_lens=torch.tensor([gt_focal, gt_focal, train_data.W / 2.0, train_data.H / 2.0,
+                                                          0.0, 0.0], dtype=torch.float32))
         torch.save(record, output_dir / "final_poses.pt")
         logger.save_summary()
         logger.close()
@@ -543,9 +674,19 @@ def build_arg_parser():
 def build_cli_parser():
     """The command line's parser: ``build_arg_parser()`` (the reference's flags and this
     project's earlier ones, in the order its callers rely on) plus the photometric loss
-    flags ``--loss`` and ``--loss_scale``."""
+    flags ``--loss`` and ``--loss_scale`` and the lens flags ``--learn_principal``,
+    ``--learn_distortion`` and ``--lens_init``."""
     ap = build_arg_parser()
     add_common_args(ap, "loss loss_scale")
+    ap.add_argument("--learn_principal", action="store_true",
+                    help="learn the principal point (cx, cy) jointly with the poses, from the image centre, in "
+                         "units of the focal length; with the pose learning rate, schedule and delay")
+    ap.add_argument("--learn_distortion", action="store_true",
+                    help="learn two radial distortion terms (k1, k2) of the NeRF-- / SCNeRF ray-side model "
+                         "jointly with the poses, from --lens_init")
+    ap.add_argument("--lens_init", type=float, nargs=2, default=(0.0, 0.0), metavar=("K1", "K2"),
+                    help="the radial terms to start from; without --learn_distortion a known calibration that "
+                         "is held fixed")
     return ap
 
 
@@ -560,7 +701,8 @@ def main(argv=None) -> None:
                                      graph=a.graph, c2f=tuple(a.c2f) if a.c2f is not None else None,
                                      fixed_small_angle=a.fixed_small_angle, learn_focal=a.learn_focal,
                                      focal_init_scale=a.focal_init_scale, distortion_weight=a.distortion_weight,
-                                     loss=a.loss, loss_scale=a.loss_scale)
+                                     loss=a.loss, loss_scale=a.loss_scale, learn_principal=a.learn_principal,
+                                     learn_distortion=a.learn_distortion, lens_init=tuple(a.lens_init))
 
     run_cli(a, lambda noise_config, world: generate_experiment_name(a.scene, noise_config, a.init_mode), call)
 

@@ -14,7 +14,10 @@ n_img = 1, 3, 300 (300: the focal partials' stride loop wraps) with one image th
 an out-of-range image index (unvalidated forward), g_rd NULL, fx == fy and fx != fy, and the
 intrinsics backward at B = 0; the four positional-encoding entry points at M = 37, C = 1 and 3,
 L = 1, 4 and 10, both include_input, both log_sampling, the window null, all ones and a ramp
-from 0.  Output buffers start as NaN (accumulated ones as zero).  There is no CPU path."""
+from 0.  Where the library has the lens entries (one built before them prints every other line
+all the same): nr_ray_directions_lens and nr_rays_from_pixels_lens_fwd/bwd in the same cases,
+at a neutral lens (fx != fy, centred, k = 0) and a live one.  Output buffers start as NaN
+(accumulated ones as zero).  There is no CPU path."""
 import hashlib
 import itertools
 import sys
@@ -34,7 +37,9 @@ def main() -> int:
     from noisy_src import _hip
     from noisy_src._hip import call, ptr
 
-    lib = _hip.load()
+    lib = _hip.load(require_all=False)  # a library of before the lens entries loads too
+    has_lens = hasattr(lib, "nr_rays_from_pixels_lens_fwd")
+    lenses = (("lens_neutral", (7.3, 5.9, 3.5, 2.5, 0.0, 0.0)), ("lens_live", (7.3, 5.9, 3.2, 2.9, 0.11, -0.03)))
     stream = _hip.stream_ptr()
     print(f"# {_hip.lib_path().name}", file=sys.stderr)
 
@@ -57,6 +62,11 @@ def main() -> int:
             d = nans(H, W, 3)
             call("nr_ray_directions_xy", H, W, fx, fy, W / 2.0, H / 2.0, ptr(d), stream)
             emit(f"ray_directions_xy/{H}x{W}/fx{fx}_fy{fy}", dirs=d)
+        for tag, lens in lenses if has_lens else ():
+            d = nans(H, W, 3)
+            call("nr_ray_directions_lens", H, W, *lens[:2], W / 2.0 - 3.5 + lens[2], H / 2.0 - 2.5 + lens[3], *lens[4:],
+                 ptr(d), stream)
+            emit(f"ray_directions_lens/{H}x{W}/{tag}", dirs=d)
 
     # ---- get_rays backward
     ws = torch.empty(int(lib.nr_get_rays_bwd_workspace_bytes()), device=DEV, dtype=torch.uint8)
@@ -88,6 +98,11 @@ def main() -> int:
                 call("nr_rays_from_pixels_intr_fwd", ptr(img), ptr(pix), ptr(poses), n_img, H, W, ptr(fxy), B, ptr(ro),
                      ptr(rd), None, stream)
             emit(f"{case}/fwd/{tag}", rays_o=ro, rays_d=rd)
+        for tag, f in lenses if has_lens else ():
+            ro, rd, lens = nans(B, 3), nans(B, 3), torch.tensor(f, device=DEV)
+            call("nr_rays_from_pixels_lens_fwd", ptr(img), ptr(pix), ptr(poses), n_img, H, W, ptr(lens), B, ptr(ro),
+                 ptr(rd), None, stream)
+            emit(f"{case}/fwd/{tag}", rays_o=ro, rays_d=rd)
 
     def pixels_bwd(case, img, pix, poses, B, n_img, g_ro, g_rd):
         for tag, f in focals:
@@ -103,6 +118,12 @@ def main() -> int:
                 call("nr_rays_from_pixels_intr_bwd", ptr(img), ptr(pix), ptr(poses), n_img, H, W, ptr(fxy), B,
                      ptr(g_ro), ptr(g_rd), ptr(g_poses), ptr(g_fxy), ptr(fws), stream)
                 emit(f"{case}/bwd/{tag}", g_poses=g_poses, g_fxy=g_fxy)
+        for tag, f in lenses if has_lens else ():
+            g_poses, g_lens, lens = torch.zeros(n_img, 4, 4, device=DEV), nans(6), torch.tensor(f, device=DEV)
+            lws = nans(int(lib.nr_rays_from_pixels_lens_bwd_workspace_bytes(n_img)) // 4)
+            call("nr_rays_from_pixels_lens_bwd", ptr(img), ptr(pix), ptr(poses), n_img, H, W, ptr(lens), B, ptr(g_ro),
+                 ptr(g_rd), ptr(g_poses), ptr(g_lens), ptr(lws), stream)
+            emit(f"{case}/bwd/{tag}", g_poses=g_poses, g_lens=g_lens)
 
     for B, n_img in itertools.product((1, 255, 257, 1000), (1, 3, 300)):
         gen = torch.Generator().manual_seed(1000 * B + n_img)
@@ -125,6 +146,12 @@ def main() -> int:
         call("nr_rays_from_pixels_intr_bwd", None, None, None, n_img, H, W, ptr(fxy), 0, None, None, ptr(g_poses),
              ptr(g_fxy), ptr(fws), stream)
         emit(f"rays_from_pixels/B0/n_img{n_img}/bwd/fxy7.3_5.9", g_poses=g_poses, g_fxy=g_fxy)
+        if has_lens:
+            g_poses, g_lens, lens = torch.zeros(n_img, 4, 4, device=DEV), nans(6), torch.tensor(lenses[1][1], device=DEV)
+            lws = nans(int(lib.nr_rays_from_pixels_lens_bwd_workspace_bytes(n_img)) // 4)
+            call("nr_rays_from_pixels_lens_bwd", None, None, None, n_img, H, W, ptr(lens), 0, None, None, ptr(g_poses),
+                 ptr(g_lens), ptr(lws), stream)
+            emit(f"rays_from_pixels/B0/n_img{n_img}/bwd/lens_live", g_poses=g_poses, g_lens=g_lens)
 
     # ---- positional encoding, plain and windowed
     M = 37
