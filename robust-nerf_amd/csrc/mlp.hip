@@ -38,6 +38,14 @@ using namespace nr;
 
 namespace {
 
+// g[0 .. n) = 0.  A kernel of this library's, not hipMemsetAsync: nr_mlp_backward_dx is
+// captured into hipGraphs, and the replayed memset node filled g_x with a stale 16-byte
+// pattern instead of zeros (tests/test_tile_patterns.py, the fp32 graph replay)
+__global__ void zero_f32_kernel(float* __restrict__ g, int64_t n) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) g[i] = 0.f;
+}
+
 bool plan_or_error(const NrMlpConfig* cfg, MlpPlan* p) {
     const char* why = "";
     if (!make_plan(cfg, p, &why)) {
@@ -301,11 +309,10 @@ int nr_mlp_backward_dx(const NrMlpConfig* cfg, const void* packed, const float* 
         // the chain writes g_x / g_d of the active tiles only: the rest are exactly zero
         for (float* g : {g_x, g_d})
             if (g) {
-                const hipError_t e = hipMemsetAsync(g, 0, sizeof(float) * 3 * static_cast<size_t>(M), s);
-                if (e != hipSuccess) {
-                    set_error("nr_mlp_backward_dx: %s", hipGetErrorString(e));
-                    return static_cast<int>(e);
-                }
+                const int64_t n = 3 * M, blocks = (n + 255) / 256;
+                hipLaunchKernelGGL(zero_f32_kernel, dim3(static_cast<unsigned>(blocks < 65536 ? blocks : 65536)), dim3(256),
+                                   0, s, g, n);
+                if (const int rc = check_launch("nr_mlp_backward_dx (zeroed input gradients)")) return rc;
             }
     }
     return launch_bwd(p, b, wx, s);

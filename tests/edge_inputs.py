@@ -597,3 +597,319 @@ def fp16_scale_case(M, B, outlier):
     g_rgb, g_sigma = fp16_upstream(M, B, outlier)
     want, stored = fp16_model_run(x, d, g_rgb, g_sigma)
     return dict(x=x, d=d, g_rgb=g_rgb, g_sigma=g_sigma, survivors=survivors, want=want, stored=stored)
+
+
+# ------------------- the skipping backward on structured active-tile patterns --
+# (test_tile_patterns.py)  A tile is 32 samples; tile_flags_kernel writes one flag byte per
+# tile (four to a flag word) and one count per 64-tile block; a dX workgroup takes W active
+# tiles (8 waves in 16 bit, 4 in fp32) of one 256-tile segment.
+TILE, WORD_TILES, BLOCK_TILES, SEG_TILES = 32, 4, 64, 256
+M_A = 10_245  # 321 tiles, two segments: segment 1 = one full block + a block of one 5-sample tile
+M_B = 20_485  # 641 tiles, three segments: segment 2 = 129 tiles, its fourth block empty
+TILE_PRECISIONS = ["bf16", "fp16", "fp32"]
+
+_FIXED_PATTERNS = {  # at M_B
+    "first_only": (0,),
+    "block_edges": (319, 320, 383, 384, 447, 448),
+    # a word boundary (3 | 4, 7 | 8), one full flag word (12 .. 15), one tile at each byte position (16, 21, 26, 31)
+    "word_edges": (3, 4, 7, 8, 12, 13, 14, 15, 16, 21, 26, 31),
+    "middle_only": (256, 259, 260, 319, 320, 383, 384, 449, 511),       # nine tiles, all in segment 1
+    "ends_only": (0, 63, 64, 200, 255, 512, 575, 576, 639, 640),        # five each in segments 0 and 2
+    "last_segment_empty": (0, 5, 63, 64, 255, 256, 300, 447, 448, 511),  # five each in segments 0 and 1
+}
+NAMED_PATTERNS = ["first_only", "last_partial_only", "seg_edges", "block_edges", "word_edges", "middle_only", "ends_only",
+                  "last_segment_empty", "per_part_3_4_5", "per_part_7_8_9", "one_full_segment", "all_but_one"]
+REFERENCE_PATTERNS = [n for n in NAMED_PATTERNS if n != "all_but_one"]  # (20k selected samples: dense run only)
+# the stale-scratch and graph-replay tests walk these in this order, refilling nothing in between
+STALE_SEQUENCE = ["all_active", "seg_edges", "none_active", "one_full_segment", "last_partial_only", "all_active"]
+
+
+def n_tiles(M):
+    return (M + TILE - 1) // TILE
+
+
+def _spread(lo, size, n):
+    """n tiles of [lo, lo + size): the first, the last and even steps between."""
+    return [lo + (i * (size - 1)) // (n - 1) for i in range(n)]
+
+
+def named_tiles(name, M=M_B):
+    """The active tiles of a named pattern, increasing.  The names of _FIXED_PATTERNS and the
+    per_part ones are sets at M_B; the others follow M: ``seg_edges`` the tile on either side
+    of every segment boundary, ``one_full_segment`` the last segment of 256 tiles (segment 1
+    at M_B, segment 0 at M_A), ``last_partial_only`` the last tile."""
+    T = n_tiles(M)
+    nseg = (T + SEG_TILES - 1) // SEG_TILES
+    if name == "all_active":
+        return tuple(range(T))
+    if name == "none_active":
+        return ()
+    if name == "last_partial_only":
+        assert M % TILE
+        return (T - 1,)
+    if name == "seg_edges":
+        return tuple(t for s in range(1, nseg) for t in (s * SEG_TILES - 1, s * SEG_TILES))
+    if name == "one_full_segment":
+        s = T // SEG_TILES - 1
+        return tuple(range(s * SEG_TILES, (s + 1) * SEG_TILES))
+    assert M == M_B, (name, M)
+    if name == "all_but_one":
+        return tuple(t for t in range(T) if t != 300)
+    if name.startswith("per_part_"):
+        counts = [int(v) for v in name.split("_")[2:]]
+        assert len(counts) == nseg
+        return tuple(t for s, n in enumerate(counts) for t in _spread(s * SEG_TILES, min(SEG_TILES, T - s * SEG_TILES), n))
+    return _FIXED_PATTERNS[name]
+
+
+# the count sweep at M_A: the first n tiles of a fixed order -- the partial last tile, both
+# sides of the segment boundary, tile 0, then a seeded permutation of the rest
+SWEEP_COUNTS = list(range(1, 2 * (n_tiles(M_A) // 16) + 2))  # 1 .. 41; tiles // 16 caps the dW chunks per job
+OTHER_MODELS = ["depth16_skips_0_3_6_9_12", "depth3_skip1_no_view_dirs", "depth2_skip0"]
+OTHER_MODEL_COUNTS = [1, 2, 7, 8, 9, 11, 12, 13, 14, 15, 19, 20, 21, 40, 41]
+OTHER_MODEL_SET = (255, 256, 320)
+OTHER_MODEL_PRECISIONS = ["bf16", "fp32"]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_order(M=M_A):
+    head = [n_tiles(M) - 1, SEG_TILES - 1, SEG_TILES, 0]
+    rest = [t for t in range(n_tiles(M)) if t not in head]
+    perm = torch.randperm(len(rest), generator=torch.Generator().manual_seed(4242)).tolist()
+    return tuple(head + [rest[i] for i in perm])
+
+
+def sweep_tiles(n, M=M_A):
+    return tuple(sorted(sweep_order(M)[:n]))
+
+
+def other_model_sets():
+    """(id, tiles) of the non-default models' runs at M_A."""
+    return [(f"count{n}", sweep_tiles(n)) for n in OTHER_MODEL_COUNTS] + [("seg_edges_last", OTHER_MODEL_SET)]
+
+
+# Which values count as zero (M_A): three tiles that are active through ONE component of
+# ONE sample -- g_sigma of sample 31 of tile 7, g_rgb[:, 2] of sample 0 of tile 256, and
+# g_sigma of the last valid row M - 1 -- alone, with a tile (130) whose upstream is -0.0
+# throughout, or with a tile (200) whose only nonzero is the fp32 denormal 1e-42 (g_sigma of
+# its sample 13).  Components: 0..2 = g_rgb columns, 3 = g_sigma.
+ZERO_SINGLES = ((7 * TILE + 31, 3), (256 * TILE, 2), (M_A - 1, 3))
+ZERO_RULE_CASES = {
+    "single_components": dict(),
+    "negative_zero_tile": dict(negzero=(130,)),
+    "denormal_only_tile": dict(denormal=((200 * TILE + 13, 3),)),
+}
+DENORMAL = 1e-42
+SINGLES_SPARE = 8  # spare selected samples per single-component row (see tile_case)
+
+
+class _Jittered(ref.MfmaEmulatedNeRF):
+    """The numerics model with every MFMA layer's pre-activation moved by ``amp`` of its size
+    (at least 1e-3): what some other summation orders do to it, as noise."""
+
+    amp, gen = 4e-6, None  # (amp carries the sign of an antithetic run)
+
+    def _lin(self, x, lin):
+        out = super()._lin(x, lin)
+        return out + out.detach().abs().clamp_min(1e-3) * self.amp * torch.randn(out.shape, generator=self.gen)
+
+
+class _JitteredEncoding(torch.nn.Module):
+    """The oracle's encoding with its sines and cosines moved by ``amp`` (absolute; the kernels'
+    hardware sine behind pe_rev's argument reduction is ~1e-6 from torch's)."""
+
+    def __init__(self, enc, gen, amp):
+        super().__init__()
+        self.enc, self.gen, self.amp, self.output_dim = enc, gen, amp, enc.output_dim
+
+    def forward(self, v):
+        e = self.enc(v)
+        noise = self.amp * torch.randn(e.shape, generator=self.gen)
+        noise[..., :v.shape[-1]] = 0.0  # the input's own columns are exact
+        return e + noise
+
+
+# JITTER_PAIRS antithetic pairs of runs: the same noise with either sign, so that a value within
+# |noise| of a rounding boundary crosses it in one run of the pair whichever side it is on.
+# One-sided runs miss half of them: with four such runs 2 of 287 GPU cases still met a fragile sample.
+JITTER_PAIRS, JITTER_AMP, JITTER_TOL = 4, 4e-6, 1e-3
+
+
+def jitter_fragile(oracle, precision, x, d):
+    """16 bit: the samples whose input gradient under the numerics model moves by more than
+    JITTER_TOL (relative, per sample) in any of 2 JITTER_PAIRS runs of the model with its sines
+    and its MFMA pre-activations jittered by +-JITTER_AMP.
+
+    Why: the model rounds the encoding, every activation and every dz to 16 bits.  A sine that
+    the hardware computes 1e-6 off, or a pre-activation that another summation order moves by
+    1e-7, can round the other way (2^-8 of its size in bf16), which moves the next layer's
+    pre-activations by 3e-5 .. 4e-4 and carries ReLUs across zero far inside mlp_selected's
+    1e-5 margin; ``sine_sensitive`` sees this only where the FORWARD moves, and a flipped
+    ReLU at z ~ 0 moves only the backward.  For most samples nothing changes at all (the median
+    move is exactly 0); for ~10 % in bf16 (2 % in fp16) the sample's backward path changes (its
+    g_x moves by 1 % .. 100 %), and among a few hundred samples ONE such sample moves the
+    trunk's parameter gradients by 1 .. 7 %.  On mlp_selected's samples the kernels measured
+    1.5 .. 4.9e-2 from the model at trunk layers on 5 of the first 97 sample sets of
+    test_tile_patterns -- the same figure for two patterns that share a sample set -- while
+    every fp32 case, every forward and the dense run of the same kernels agreed; the model
+    jittered like this is as far from itself.  Such a sample has no reference to 1.5e-2, so the
+    patterns are built without them; the kernels then stay within 1.5e-3 (bf16) and 4.8e-3
+    (fp16) of the model on every one of test_tile_patterns' 155 16-bit sample sets."""
+    model = ref.mfma_emulated_nerf(copy.deepcopy(oracle), precision)
+    g_rgb, g_sigma = mlp_upstream(x.shape[0], seed=4300, scale=upstream_scale(precision))
+
+    def input_grads(m):
+        xr, dr = x.clone().requires_grad_(True), d.clone().requires_grad_(True)
+        wr, ws = m(xr, dr)
+        ((wr * g_rgb).sum() + (ws * g_sigma).sum()).backward()
+        return xr.grad if dr.grad is None else torch.cat([xr.grad, dr.grad], -1)
+
+    g0 = input_grads(model)
+    worst = torch.zeros(x.shape[0])
+    for k in range(2 * JITTER_PAIRS):
+        gen = torch.Generator().manual_seed(4400 + k // 2)  # the pair draws the same noise
+        amp = JITTER_AMP * (1 - 2 * (k % 2))
+        alt = copy.deepcopy(oracle)
+        alt.pos_encoder = _JitteredEncoding(oracle.pos_encoder, gen, amp)
+        alt.dir_encoder = _JitteredEncoding(oracle.dir_encoder, gen, amp)
+        jit = _Jittered(alt, model.dtype, model.scale)
+        jit.amp, jit.gen = amp, gen
+        worst = torch.maximum(worst, (input_grads(jit) - g0).norm(dim=-1) / g0.norm(dim=-1).clamp_min(1e-30))
+    return worst > JITTER_TOL
+
+
+TILE_POOL = 41 * TILE  # the largest sample count of the sweeps at M_A
+
+
+@functools.lru_cache(maxsize=None)
+def _stable_pool(precision, n, case):
+    xs, ds, _ = mlp_selected(precision, (2 * n if n <= TILE_POOL else n + n // 2) + 32, case)
+    keep = ~jitter_fragile(oracle_net(precision, case=case), precision, xs, ds)
+    return xs[keep].contiguous(), ds[keep].contiguous()
+
+
+def tile_selected(precision, A, case=None):
+    """(x, d, survivors) of the A samples a tile pattern scatters: fp32 mlp_selected(precision,
+    A, case); 16 bit the first A samples of a pool, the samples of mlp_selected(precision,
+    2 n + 32, case) that are not ``jitter_fragile``, with n = TILE_POOL for A up to it (the sets
+    of the sweeps are nested, and the filter runs once per model); above it n = A of 1.5 A + 32.
+    survivors: the size of the pool."""
+    if precision == "fp32":
+        return mlp_selected(precision, A, case)
+    xs, ds = _stable_pool(precision, TILE_POOL if A <= TILE_POOL else A, case)
+    return xs[:A].contiguous(), ds[:A].contiguous(), xs.shape[0]
+
+
+def tile_rows(tiles, M):
+    """The valid rows of ``tiles``, increasing."""
+    if not len(tiles):
+        return torch.zeros(0, dtype=torch.long)
+    r = (torch.tensor(sorted(tiles))[:, None] * TILE + torch.arange(TILE)[None]).reshape(-1)
+    return r[r < M]
+
+
+def expected_active(g_rgb, g_sigma):
+    """Per tile: any component ``!= 0`` on the host (so -0.0 is zero and a denormal or NaN is
+    not) -> bool per tile."""
+    M = g_rgb.shape[0]
+    nz = (g_rgb != 0).any(-1) | (g_sigma.reshape(M, -1) != 0).any(-1)
+    return torch.nn.functional.pad(nz, (0, (-M) % TILE)).reshape(-1, TILE).any(-1)
+
+
+def upstream_scale(precision):
+    """test_mlp_ragged's magnitudes: 1 for fp32, a mean loss over 4096 rays in 16 bit."""
+    return 1.0 if precision == "fp32" else 2.0 / (3 * 4096)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_case(precision, M, tiles, case=None, singles=(), negzero=(), denormal=(), selected=True):
+    """Inputs of one active-tile pattern: M rows of x, d, g_rgb, g_sigma on the host.
+
+    ``tiles`` are active throughout; ``singles`` = (row, component) are samples with that one
+    component nonzero in an otherwise zero tile.  Those rows -- ``rows``, A of them -- hold the
+    A kink-free samples of tile_selected(precision, A, case), in order, and the upstream
+    gradient mlp_upstream(A) (singles: masked to the one component); with ``selected=False``
+    (patterns that are compared with the dense run only) they keep the candidates below and
+    take mlp_upstream(M).  Every other row holds an mlp_candidates sample with a zero
+    upstream gradient: +0.0, or -0.0 throughout the tiles ``negzero``, or DENORMAL at the
+    (row, component) entries of ``denormal``.  A sample with zero upstream gradient
+    contributes exactly nothing, so ``want``, reference_outputs on the A rows alone, is the
+    reference of the whole pattern (a DENORMAL entry adds less than 1e-38 to any sum).
+    ``active``: expected_active of the host tensors; ``count`` their number."""
+    tiles = tuple(sorted(tiles))
+    T = n_tiles(M)
+    assert all(0 <= t < T for t in tiles) and len(set(tiles)) == len(tiles)
+    rows = torch.cat([tile_rows(tiles, M), torch.tensor([r for r, _ in singles], dtype=torch.long)]).sort().values
+    A = rows.numel()
+    assert rows.unique().numel() == A
+    x, d = mlp_candidates(M, seed=4000 + M)
+    g_rgb, g_sigma = torch.zeros(M, 3), torch.zeros(M, 1)
+    scale = upstream_scale(precision)
+    out = dict(tiles=tiles, rows=rows, A=A, survivors=None, want=None)
+    if selected and A:
+        xs, ds, out["survivors"] = tile_selected(precision, A + SINGLES_SPARE * len(singles), case)
+        if singles:
+            # a sample that is active through g_sigma alone needs sigma > 0 (ReLU'), or it is
+            # active and contributes nothing: such rows take the next sample with a live sigma
+            zr, zs = torch.zeros(xs.shape[0], 3), torch.zeros(xs.shape[0], 1)
+            live = reference_outputs(oracle_net(precision, case=case), precision, xs, ds, zr, zs)["sigma"] > 0
+            sigma_only = {r for r, comp in singles if comp == 3}
+            free, order = list(range(xs.shape[0])), []
+            for r in rows.tolist():
+                order.append(next(i for i in free if live[i] or r not in sigma_only))
+                free.remove(order[-1])
+            xs, ds = xs[order], ds[order]
+        assert xs.shape[0] == A, "too few kink-free candidates"
+        out.update(sel_x=xs, sel_d=ds)
+        ur, us = mlp_upstream(A, seed=4100 + A, scale=scale)
+        x[rows], d[rows] = xs, ds
+        g_rgb[rows], g_sigma[rows] = ur, us
+    elif A:
+        ur, us = mlp_upstream(M, seed=4100 + M, scale=scale)
+        g_rgb[rows], g_sigma[rows] = ur[rows], us[rows]
+    for r, comp in singles:
+        keep = torch.cat([g_rgb[r], g_sigma[r]])[comp].clone()
+        assert keep != 0
+        g_rgb[r], g_sigma[r] = 0.0, 0.0
+        (g_rgb[r] if comp < 3 else g_sigma[r])[comp % 3] = keep
+    for t in negzero:
+        g_rgb[t * TILE:(t + 1) * TILE] = -0.0
+        g_sigma[t * TILE:(t + 1) * TILE] = -0.0
+    for r, comp in denormal:
+        (g_rgb[r] if comp < 3 else g_sigma[r])[comp % 3] = DENORMAL
+    active = expected_active(g_rgb, g_sigma)
+    out.update(x=x, d=d, g_rgb=g_rgb, g_sigma=g_sigma, active=active, count=int(active.sum()))
+    if selected and A:
+        out["want"] = reference_outputs(oracle_net(precision, case=case), precision, x[rows], d[rows], g_rgb[rows],
+                                        g_sigma[rows])
+    return out
+
+
+def named_case(precision, name, M=M_B, selected=None):
+    selected = name in REFERENCE_PATTERNS if selected is None else selected
+    return tile_case(precision, M, named_tiles(name, M), selected=selected)
+
+
+def zero_rule_case(precision, name):
+    return tile_case(precision, M_A, (), singles=ZERO_SINGLES, **ZERO_RULE_CASES[name])
+
+
+def tile_moves(c, precision, case, tile):
+    """How far the reference's parameter gradients move when the upstream gradient of one
+    active tile is zeroed: name -> |g - g_without| / |g|.  The reference is a sum over
+    samples (every rounding of the numerics model is per sample), so g - g_without is the
+    reference of that tile's rows alone; test_edge_inputs_host holds this shortcut to the
+    recomputation itself."""
+    rows = c["rows"]
+    own = rows[(rows // TILE) == tile]
+    assert own.numel() > 0
+    part = reference_outputs(oracle_net(precision, case=case), precision, c["x"][own], c["d"][own], c["g_rgb"][own],
+                             c["g_sigma"][own])
+    return {n: (g.double().norm() / w.double().norm().clamp_min(1e-300)).item()
+            for (n, g), (_, w) in zip(part["grads"], c["want"]["grads"])}
+
+
+def teeth_tiles(c):
+    """The first, a middle and the last tile that holds reference rows."""
+    ts = sorted(set((c["rows"] // TILE).tolist()))
+    return sorted({ts[0], ts[len(ts) // 2], ts[-1]})

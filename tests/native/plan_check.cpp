@@ -5,6 +5,9 @@
 // and reduce arguments: the same pure builders, called here without a device).
 //   plan_check pos_freqs dir_freqs n_layers skip_mask use_view_dirs precision
 //   plan_check --sweep     the same checks, in this one process, over the whole config space
+//   plan_check --list-lds pos_freqs dir_freqs n_layers skip_mask use_view_dirs precision M...
+//                          per M: the tiles, the dW chunks per job and the LDS offset the dW
+//                          kernel stages its active-tile list to (0: it reads the list global)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -304,8 +307,27 @@ static int sweep() {
     return failures != 0;
 }
 
+static int list_lds(int argc, char** argv) {
+    NrMlpConfig c{atoi(argv[2]), atoi(argv[3]), 256, atoi(argv[4]), (uint32_t)atoi(argv[5]), atoi(argv[6]), atoi(argv[7])};
+    MlpPlan p; const char* why = "";
+    if (!make_plan(&c, &p, &why)) { printf("plan fail %s\n", why); return 1; }
+    for (int i = 8; i < argc; ++i) {
+        const MlpSizes z = make_sizes(p, atol(argv[i]));
+        static DwArgs w;
+        int nwg = 0;
+        size_t lds = 0;
+        if (!dw_args(p, z, reinterpret_cast<const char*>(uintptr_t(1) << 40), reinterpret_cast<char*>(uintptr_t(1) << 44), &w,
+                     &nwg, &lds, &why)) { printf("dw_args fail %s\n", why); return 1; }
+        printf("M %ld tiles %ld nseg %ld list_lds %d chunks", atol(argv[i]), (long)z.tiles, (long)z.nseg, w.list_lds);
+        for (int j = 0; j < p.n_jobs; ++j) printf(" %d", z.job_chunks[j]);
+        printf("\n");
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 2 && !strcmp(argv[1], "--sweep")) return sweep();
+    if (argc >= 9 && !strcmp(argv[1], "--list-lds")) return list_lds(argc, argv);
     NrMlpConfig c{10, 4, 256, 8, 1u << 4, 1, 1};
     if (argc == 7) c = {atoi(argv[1]), atoi(argv[2]), 256, atoi(argv[3]), (uint32_t)atoi(argv[4]), atoi(argv[5]), atoi(argv[6])};
     MlpPlan p; const char* why = "";

@@ -385,3 +385,193 @@ def test_fp16_model_finite_range():
     tiny = 2.0 / (3 * 4096) * 2.0 ** -14
     want, stored = ei.fp16_model_run(x, d, g_rgb * tiny, g_sigma * tiny)
     assert _model_is_finite(want, stored) and all(torch.count_nonzero(v) > 0 for v in stored)
+
+
+# ------------------------------ active-tile patterns (test_tile_patterns.py) --
+def _per(tiles, size):
+    out = {}
+    for t in tiles:
+        out[t // size] = out.get(t // size, 0) + 1
+    return out
+
+
+def test_named_patterns_are_what_their_names_say():
+    """The sizes, and per name the tile set with its active tiles per 256-tile segment, per
+    64-tile block and per 4-tile flag word."""
+    T, seg, blk, word = ei.n_tiles(ei.M_B), ei.SEG_TILES, ei.BLOCK_TILES, ei.WORD_TILES
+    assert (ei.n_tiles(ei.M_A), ei.M_A % 32, ei.n_tiles(ei.M_B), ei.M_B % 32) == (321, 5, 641, 5)
+    assert ei.n_tiles(ei.M_A) - seg == 65 and T - 2 * seg == 129  # segment 1 of M_A; segment 2 of M_B: 64 + 64 + 1 + 0
+    nt = {n: ei.named_tiles(n) for n in ei.NAMED_PATTERNS}
+    for n, t in nt.items():
+        assert list(t) == sorted(set(t)) and 0 <= t[0] and t[-1] < T, n
+    assert nt["first_only"] == (0,) and nt["last_partial_only"] == (640,)
+    assert nt["seg_edges"] == (255, 256, 511, 512) and _per(nt["seg_edges"], seg) == {0: 1, 1: 2, 2: 1}
+    assert nt["block_edges"] == (319, 320, 383, 384, 447, 448)
+    assert _per(nt["block_edges"], seg) == {1: 6} and _per(nt["block_edges"], blk) == {4: 1, 5: 2, 6: 2, 7: 1}
+    assert nt["word_edges"] == (3, 4, 7, 8, 12, 13, 14, 15, 16, 21, 26, 31)
+    assert _per(nt["word_edges"], word) == {0: 1, 1: 2, 2: 1, 3: 4, 4: 1, 5: 1, 6: 1, 7: 1}
+    assert [t % word for t in (16, 21, 26, 31)] == [0, 1, 2, 3]  # one tile at each byte position
+    assert _per(nt["middle_only"], seg) == {1: 9}
+    assert _per(nt["ends_only"], seg) == {0: 5, 2: 5} and 640 in nt["ends_only"]
+    assert _per(nt["last_segment_empty"], seg) == {0: 5, 1: 5}
+    for name, counts in (("per_part_3_4_5", (3, 4, 5)), ("per_part_7_8_9", (7, 8, 9))):
+        assert _per(nt[name], seg) == dict(enumerate(counts))
+        for s in range(3):  # spread over the segment: its first and its last tile, every block touched
+            own = [t for t in nt[name] if t // seg == s]
+            assert own[0] == s * seg and own[-1] == min(T, (s + 1) * seg) - 1
+            assert len(_per(own, blk)) >= min(3, len(own))
+    assert nt["one_full_segment"] == tuple(range(256, 512))
+    assert nt["all_but_one"] == tuple(t for t in range(641) if t != 300)
+    assert ei.REFERENCE_PATTERNS == [n for n in ei.NAMED_PATTERNS if n != "all_but_one"] and len(ei.NAMED_PATTERNS) == 12
+    # the names that follow M, at M_A (the graph test's sequence)
+    assert ei.named_tiles("seg_edges", ei.M_A) == (255, 256) and ei.named_tiles("last_partial_only", ei.M_A) == (320,)
+    assert ei.named_tiles("one_full_segment", ei.M_A) == tuple(range(256))
+    assert ei.named_tiles("all_active", ei.M_A) == tuple(range(321)) and ei.named_tiles("none_active", ei.M_A) == ()
+    assert ei.STALE_SEQUENCE == ["all_active", "seg_edges", "none_active", "one_full_segment", "last_partial_only",
+                                 "all_active"]
+
+
+def test_sweep_order_and_counts():
+    """Tiles 320, 255, 256, 0, then a permutation of the rest; counts 1 .. 41 = 2 (tiles // 16) + 1,
+    which includes every other model's counts; (255, 256, 320) is the sweep's own first three."""
+    order = ei.sweep_order()
+    assert order[:4] == (320, 255, 256, 0) and sorted(order) == list(range(321))
+    assert ei.SWEEP_COUNTS == list(range(1, 42)) and set(ei.OTHER_MODEL_COUNTS) <= set(ei.SWEEP_COUNTS)
+    assert ei.sweep_tiles(3) == ei.OTHER_MODEL_SET == (255, 256, 320)
+    assert ei.OTHER_MODEL_COUNTS == [1, 2, 7, 8, 9, 11, 12, 13, 14, 15, 19, 20, 21, 40, 41]
+    assert [n for n in ei.OTHER_MODELS if n not in ei.CONFIG_CASES] == []
+
+
+def _check_tile_case(c, precision, M, case=None, singles=0, kinks=False):
+    """The scattered samples are the selected ones, in order; every other row has a zero
+    upstream gradient; count and rows are what the tile set says."""
+    rows, A = c["rows"], c["A"]
+    partial = (ei.n_tiles(M) - 1) in c["tiles"]
+    assert A == 32 * len(c["tiles"]) - (27 if partial else 0) + (A - ei.tile_rows(c["tiles"], M).numel())
+    xs, ds, survivors = ei.tile_selected(precision, A + ei.SINGLES_SPARE * singles, case)
+    assert survivors >= xs.shape[0] >= A and c["survivors"] == survivors
+    if not singles:
+        assert torch.equal(c["sel_x"], xs) and torch.equal(c["sel_d"], ds)
+    for sx, sd in zip(c["sel_x"], c["sel_d"]):  # (single-component rows: A of the pool, see tile_case)
+        assert ((xs == sx).all(-1) & (ds == sd).all(-1)).sum() == 1
+    assert torch.equal(c["x"][rows], c["sel_x"]) and torch.equal(c["d"][rows], c["sel_d"])
+    if kinks and A <= 1312:  # (the named patterns and the zero rule; the sweeps take the same path)
+        oracle = ei.oracle_net(precision, case=case)
+        if precision == "fp32":
+            assert torch.all(ei.kink_free(oracle, c["sel_x"], c["sel_d"], 2e-6))
+        else:
+            assert torch.all(ei.model_kink_free(oracle, precision, c["sel_x"], c["sel_d"], 1e-5))
+    other = torch.ones(M, dtype=torch.bool)
+    other[rows] = False
+    bx, bd = ei.mlp_candidates(M, seed=4000 + M)
+    assert torch.equal(c["x"][other], bx[other]) and torch.equal(c["d"][other], bd[other])
+    up = torch.cat([c["g_rgb"], c["g_sigma"]], -1)
+    assert (up[rows] != 0).any(-1).all()
+    quiet = up[other]
+    assert ((quiet == 0) | (quiet.abs() == ei.DENORMAL)).all()
+    assert c["count"] == int(c["active"].sum()) and c["active"].shape == (ei.n_tiles(M),)
+    holding, active = set((rows // 32).tolist()), set(c["active"].nonzero().reshape(-1).tolist())
+    denormal_only = set((torch.nonzero((up != 0).any(-1) & other).reshape(-1) // 32).tolist()) - holding
+    assert holding <= active and active - holding == denormal_only  # (active without a reference row)
+
+
+def _toothless(c, precision, case):
+    """[(tile, largest move)] of teeth_tiles whose zeroed upstream moves no parameter's
+    reference gradient by more than 3e-2: twice the loosest bound (1.5e-2), so a lost or a
+    doubled tile cannot pass the comparison."""
+    bad = []
+    for t in ei.teeth_tiles(c):
+        worst = max(ei.tile_moves(c, precision, case, t).values())
+        if not worst > 3e-2:
+            bad.append((t, worst))
+    return bad
+
+
+@pytest.mark.parametrize("precision", ei.TILE_PRECISIONS)
+def test_named_pattern_cases_have_teeth(precision):
+    """Every named pattern that is compared with the reference, at M_B: the builder's output
+    is what it says, enough candidates survive the selection, and zeroing the first, a
+    middle or the last active tile moves a parameter gradient of the reference by > 3e-2."""
+    for name in ei.REFERENCE_PATTERNS:
+        c = ei.named_case(precision, name)
+        assert c["tiles"] == ei.named_tiles(name) and c["count"] == len(c["tiles"]), name
+        assert c["active"].nonzero().reshape(-1).tolist() == list(c["tiles"]), name
+        _check_tile_case(c, precision, ei.M_B, kinks=True)
+        assert not _toothless(c, precision, None), name
+    c = ei.named_case(precision, "all_but_one")
+    assert c["want"] is None and c["count"] == 640 and not c["active"][300] and c["A"] == 640 * 32 - 27
+
+
+@pytest.mark.parametrize("precision", ei.TILE_PRECISIONS)
+def test_count_sweep_cases_have_teeth(precision):
+    """Counts 1 .. 41 at M_A for the default model.  The smallest move over all counts and
+    zeroed tiles: 0.068 (38 tiles) / 0.070 (16) / 0.069 (23) in fp32 / bf16 / fp16."""
+    for n in ei.SWEEP_COUNTS:
+        c = ei.tile_case(precision, ei.M_A, ei.sweep_tiles(n))
+        assert c["count"] == n
+        _check_tile_case(c, precision, ei.M_A)
+        assert not _toothless(c, precision, None), n
+
+
+@pytest.mark.parametrize("precision", ei.OTHER_MODEL_PRECISIONS)
+@pytest.mark.parametrize("case", ei.OTHER_MODELS)
+def test_other_model_cases_have_teeth(case, precision):
+    """The three non-default models at M_A, every count of OTHER_MODEL_COUNTS and the set
+    (255, 256, 320): the condition holds at every count (the smallest move is 0.052, depth 2
+    in bf16 at 19 tiles), so no case's largest count was reduced."""
+    for label, tiles in ei.other_model_sets():
+        c = ei.tile_case(precision, ei.M_A, tiles, case)
+        assert c["count"] == len(tiles)
+        _check_tile_case(c, precision, ei.M_A, case)
+        for k in ("g_x", "g_d"):
+            assert (c["want"][k] is not None) == (k == "g_x" or case != "depth3_skip1_no_view_dirs")
+        assert not _toothless(c, precision, case), (label, _toothless(c, precision, case))
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp32"])
+def test_zero_rule_cases(precision):
+    """Three tiles active through one component of one sample (g_sigma of a tile's sample 31,
+    g_rgb[:, 2] of a tile's sample 0, g_sigma of row M - 1); a tile of -0.0 is not active on
+    the host's ``!= 0`` and a tile whose only nonzero is 1e-42 (an fp32 denormal) is.  Each of
+    the three single samples carries > 3e-2 of some parameter's reference gradient."""
+    M = ei.M_A
+    assert [(r // 32, r % 32, k) for r, k in ei.ZERO_SINGLES] == [(7, 31, 3), (256, 0, 2), (320, 4, 3)]
+    assert ei.ZERO_SINGLES[2][0] == M - 1 and 0 < ei.DENORMAL < FLT_MIN
+    assert torch.tensor(ei.DENORMAL, dtype=torch.float32) != 0  # not flushed on the host either
+    want_active = {"single_components": [7, 256, 320], "negative_zero_tile": [7, 256, 320],
+                   "denormal_only_tile": [7, 200, 256, 320]}
+    for name in ei.ZERO_RULE_CASES:
+        c = ei.zero_rule_case(precision, name)
+        up = torch.cat([c["g_rgb"], c["g_sigma"]], -1)
+        assert c["A"] == 3 and c["rows"].tolist() == [r for r, _ in ei.ZERO_SINGLES]
+        for r, k in ei.ZERO_SINGLES:
+            assert torch.count_nonzero(up[r // 32 * 32: r // 32 * 32 + 32]) == 1 and up[r, k] != 0
+        assert c["active"].nonzero().reshape(-1).tolist() == want_active[name] and c["count"] == len(want_active[name])
+        _check_tile_case(c, precision, M, singles=len(ei.ZERO_SINGLES), kinks=True)
+        assert not _toothless(c, precision, None), name
+        if name == "negative_zero_tile":
+            t = up[130 * 32: 131 * 32]
+            assert torch.all(t == 0) and torch.all(torch.signbit(t))
+        if name == "denormal_only_tile":
+            t = up[200 * 32: 201 * 32]
+            assert torch.count_nonzero(t) == 1 and t[13, 3] == ei.DENORMAL
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp32"])
+def test_tile_moves_is_the_recomputed_reference(precision):
+    """edge_inputs.tile_moves takes the reference of the zeroed tile's rows alone for the
+    difference of the two references; here the reference IS recomputed with that tile's
+    upstream gradient zeroed (per_part_3_4_5, its middle tile), and the two agree to 1e-3 of
+    the move itself."""
+    c = ei.named_case(precision, "per_part_3_4_5")
+    tile = ei.teeth_tiles(c)[1]
+    rows = c["rows"]
+    g_rgb, g_sigma = c["g_rgb"].clone(), c["g_sigma"].clone()
+    g_rgb[tile * 32: tile * 32 + 32] = 0
+    g_sigma[tile * 32: tile * 32 + 32] = 0
+    without = ei.reference_outputs(ei.oracle_net(precision), precision, c["x"][rows], c["d"][rows], g_rgb[rows], g_sigma[rows])
+    moves = ei.tile_moves(c, precision, None, tile)
+    for (n, g), (_, w) in zip(without["grads"], c["want"]["grads"]):
+        literal = ei.rel(g, w)
+        assert abs(literal - moves[n]) <= 1e-3 * moves[n] + 1e-7, (n, literal, moves[n])
+    assert max(moves.values()) > 3e-2

@@ -70,10 +70,10 @@ def _same_bits(a, b):
 
 
 def mlp_raw(precision, M, x, d, g_rgb, g_sigma, *, rgb, sigma, saved, workspace, g_x, g_d, g_params, dense,
-            case=None):
+            case=None, read_count=True):
     """The forward and the split backward on caller-supplied buffers, as
     noisy_src.model._MLPFunction runs them.  Returns the active-tile count the dX launch
-    left in the workspace."""
+    left in the workspace (``read_count=False``: launches only, nothing read back)."""
     from noisy_src import _hip
     from noisy_src._hip import call, ptr
     _, net, packed = _net(precision, case)
@@ -87,42 +87,65 @@ def mlp_raw(precision, M, x, d, g_rgb, g_sigma, *, rgb, sigma, saved, workspace,
          ptr(g_rgb), ptr(g_sigma), ptr(g_x), ptr(g_d), ptr(workspace), st)
     call("nr_mlp_backward_dw", c, M, ptr(saved), ptr(workspace), st)
     call("nr_mlp_backward_reduce", c, M, ptr(workspace), ptr(g_params), st)
-    off = int(_hip.load().nr_mlp_active_tiles_offset(c, M))
+    return active_tile_count(precision, M, workspace, case) if read_count else None
+
+
+def active_tile_count(precision, M, workspace, case=None):
+    """The active-tile count the last dX launch left in ``workspace`` (a read-back)."""
+    from noisy_src import _hip
+    off = int(_hip.load().nr_mlp_active_tiles_offset(ctypes.byref(_net(precision, case)[1]._nr_cfg), M))
     return int(workspace[off:off + 4].view(torch.int32).item())
 
 
-def _run(precision, M, x, d, g_rgb, g_sigma, *, tail=0.0, poison=False, dense=1, want_in=True, case=None):
-    """One forward + backward of the first M rows of the inputs.  The input buffers are
-    padded to whole tiles with ``tail`` behind row M; outputs have GUARD sentinel rows.
-    A config without view directions has no g_d."""
+def _padded(t, M, width, tail):
+    """The first M rows of ``t`` in a buffer of whole tiles, ``tail`` behind row M."""
+    buf = torch.full(((M + 31) // 32 * 32, width), tail)
+    buf[:M] = t[:M].reshape(M, width)
+    return buf.to(DEV)
+
+
+def _buffers(precision, M, *, poison=False, want_in=True, case=None):
+    """saved, workspace (zeros, or 0xFF bytes with ``poison``) and the outputs of M samples
+    with GUARD sentinel rows.  A config without view directions has no g_d."""
     from noisy_src import _hip
     _, net, _ = _net(precision, case)
     cfg = ctypes.byref(net._nr_cfg)
-    Mp = (M + 31) // 32 * 32
-
-    def padded(t, width):
-        buf = torch.full((Mp, width), tail)
-        buf[:M] = t[:M].reshape(M, width)
-        return buf.to(DEV)
-
     fill = poisoned if poison else (lambda n: torch.zeros(int(n), dtype=torch.uint8, device=DEV))
-    saved = fill(_hip.load().nr_mlp_saved_bytes(cfg, M))
-    ws = fill(_hip.load().nr_mlp_workspace_bytes(cfg, M))
     o = dict(rgb=guarded((M, 3), GUARD), sigma=guarded((M,), GUARD), g_params=guarded((net._param_count,), 64))
     if want_in:
         o.update(g_x=guarded((M, 3), GUARD))
         if net.config.use_view_dirs:
             o.update(g_d=guarded((M, 3), GUARD))
-    count = mlp_raw(precision, M, padded(x, 3), padded(d, 3), padded(g_rgb, 3), padded(g_sigma, 1),
-                    rgb=o["rgb"].buf, sigma=o["sigma"].buf, saved=saved, workspace=ws,
-                    g_x=o["g_x"].buf if want_in else None, g_d=o["g_d"].buf if "g_d" in o else None,
-                    g_params=o["g_params"].buf, dense=dense, case=case)
+    return dict(saved=fill(_hip.load().nr_mlp_saved_bytes(cfg, M)), ws=fill(_hip.load().nr_mlp_workspace_bytes(cfg, M)),
+                out=o)
+
+
+def _run_on(bufs, precision, M, x, d, g_rgb, g_sigma, *, tail=0.0, dense=1, case=None):
+    """One forward + backward of the first M rows of the inputs on the buffers of
+    ``_buffers``, as they are: nothing is refilled, so a second run sees what the first left
+    in saved, workspace and the outputs.  The input buffers are padded to whole tiles with
+    ``tail`` behind row M."""
+    o = bufs["out"]
+    count = mlp_raw(precision, M, _padded(x, M, 3, tail), _padded(d, M, 3, tail), _padded(g_rgb, M, 3, tail),
+                    _padded(g_sigma, M, 1, tail), rgb=o["rgb"].buf, sigma=o["sigma"].buf, saved=bufs["saved"],
+                    workspace=bufs["ws"], g_x=o["g_x"].buf if "g_x" in o else None,
+                    g_d=o["g_d"].buf if "g_d" in o else None, g_params=o["g_params"].buf, dense=dense, case=case)
     torch.cuda.synchronize()
+    return _results(o, count)
+
+
+def _results(o, count):
     for v in o.values():
         v.check()  # nothing written behind row M
     res = {k: v.out.cpu() for k, v in o.items()}
     res["count"] = count
     return res
+
+
+def _run(precision, M, x, d, g_rgb, g_sigma, *, tail=0.0, poison=False, dense=1, want_in=True, case=None):
+    """``_run_on`` fresh buffers."""
+    return _run_on(_buffers(precision, M, poison=poison, want_in=want_in, case=case), precision, M, x, d, g_rgb, g_sigma,
+                   tail=tail, dense=dense, case=case)
 
 
 # ------------------------------------------------- 1. padding independence --

@@ -100,3 +100,45 @@ def test_sweep_of_the_whole_config_space(plan_check):
     assert tot["failures"] == 0 and tot["refused_valid"] == 440 and tot["accepted"] == n_valid - 440
     assert tot["total"] == tot["accepted"] + tot["refused_valid"] + tot["refused_invalid"]
     assert lines[-1] == "sweep max n_jobs 24 of 24 n_red 20 of 20 fwd_chunks 159 bwd_chunks 140 of 176"
+
+
+# the models of tests/test_tile_patterns.py (edge_inputs.OTHER_MODELS and the default one):
+# n_layers, skip_mask, use_view_dirs
+TILE_PATTERN_MODELS = {"default": (8, 1 << 4, 1), "depth16_skips_0_3_6_9_12": (16, 0b1001001001001, 1),
+                       "depth3_skip1_no_view_dirs": (3, 1 << 1, 0), "depth2_skip0": (2, 1 << 0, 1)}
+
+
+@pytest.mark.parametrize("prec", [0, 1, 2], ids=["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("model", list(TILE_PATTERN_MODELS))
+def test_tile_pattern_sizes_stage_the_dw_list_in_lds(plan_check, model, prec):
+    """``plan_check --list-lds``: at the two sizes of test_tile_patterns.py (10,245 and 20,485
+    samples: 321 tiles in two segments, 641 in three) every model that file runs copies its dW
+    chunk's list entries into LDS (list_lds != 0), so the form that reads the list from global
+    memory is none of its cases; and the dW chunks per job at M = 10,245 are the ones its
+    count sweeps are built around (tiles // 16 = 20 caps them)."""
+    n, mask, vd = TILE_PATTERN_MODELS[model]
+    r = subprocess.run([str(plan_check), "--list-lds", "10", "4", str(n), str(mask), str(vd), str(prec), "10245", "20485"],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = [dict(zip(ln.split()[0:8:2], map(int, ln.split()[1:8:2])), chunks=list(map(int, ln.split()[9:])))
+            for ln in r.stdout.splitlines()]
+    assert [(w["M"], w["tiles"], w["nseg"]) for w in rows] == [(10245, 321, 2), (20485, 641, 3)]
+    assert all(w["list_lds"] > 0 for w in rows), rows
+    chunks = set(rows[0]["chunks"])
+    if model == "depth16_skips_0_3_6_9_12":
+        assert len(rows[0]["chunks"]) == 20 + (prec == 0) and chunks == ({7, 13, 14} if prec == 0 else {12})
+    else:
+        assert chunks == {20}
+    assert max(rows[1]["chunks"]) <= 641 // 16
+
+
+def test_where_the_global_dw_list_begins(plan_check):
+    """The default model's first M at which the dW list no longer fits in LDS beside the
+    staging ring (list_lds == 0), the figure test_tile_patterns.py's docstring gives: 49,921
+    tiles in fp32, 96,001 in 16 bit."""
+    for prec, first in ((0, 1_597_441), (1, 3_072_001), (2, 3_072_001)):
+        r = subprocess.run([str(plan_check), "--list-lds", "10", "4", "8", "16", "1", str(prec), str(first - 1), str(first)],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+        below, at = [int(ln.split()[7]) for ln in r.stdout.splitlines()]
+        assert below > 0 and at == 0, r.stdout

@@ -14,7 +14,10 @@ backward does):
 * no tile active: exactly zero gradients;
 * the same on a trained state through the whole render + backward (the zeros come from the
   compositing itself there), and the count the kernels ran on equals the tiles with a
-  nonzero incoming gradient."""
+  nonzero incoming gradient.
+
+test_tile_patterns.py places the active tiles on the flag-word, block and segment edges,
+sweeps their count across the dW chunk counts and compares with an independent reference."""
 
 import pytest
 import torch
